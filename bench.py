@@ -13,27 +13,32 @@ line (cfg3's seed-3 set, pinned by tests/golden/large_hashes.json), rank r
 holding file rows [50M r / N, 50M (r+1) / N), classified by rk_classify_sharded
 with RCCL all-to-alls over xGMI (xStart/10 slices, X/Y halo exchange,
 cross-slice roots, gid-range member sort; DESIGN.md "Multi-GPU") -- strong
-scaling.  After the timed region every rank's output share is gathered to rank
-0 and the whole result's digest is checked against the reference's (`parity`).
+scaling.  With `--full`, after the timed region every rank's output share is
+gathered to rank 0 and the whole result's digest is checked against the
+reference's (`parity`).
 The same run first measures
 `replicas`: every rank classifies its own independent 50M set (no data-path
 collective), reported beside the value under `replicas`, never as it: if the
 sharded leg fails, `value` is null and the error is reported.  A gloo barrier
 brackets every timed region and the max time over ranks is reported.
 
-Rank 0 prints ONE JSON line.  Extra keys: `roofline` for the kernel with the
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the steps
+and prints the headline keys with `roofline` for the kernel with the
 most device time per step (algorithmic bytes per launch / HIP-event launch time
 measured inside the timed steps -- only that kernel's launches carry events
 there, so the timers cost the step little; PMC HBM traffic from
-profiles/traffic.json), `kernels` (every kernel, from PROFILED_STEPS further
+profiles/traffic.json) and `phases_ms` (per-step device time per phase, from
+the same steps).  `--dump-outputs DIR` also writes what the last timed step
+returned (`dump_outputs`).  Everything below takes runs of its own and is
+measured only with `--full`: `kernels` (every kernel, from PROFILED_STEPS further
 steps with every launch timed, after the timed region),
 `cpu_baseline` (1 core of this host: the reference itself,
 oracle/_ref/ref_driver, on a bounded sample of the workload as the value; the
 in-repo restatement on the SAME arrays the GPU classified beside it, result
 compared; this host's nproc), `parity` (the timed
 steps' result digest against the reference's, tests/golden/large_hashes.json),
-`host_to_host_fragments_per_s` (rk_classify from host buffers, PCIe included),
-`phases_ms` (per-step device time per phase).
+`host_to_host_fragments_per_s` (rk_classify from host buffers, PCIe included).
+At N > 1 `--full` also gathers the sharded result for its `parity`.
 """
 from __future__ import annotations
 
@@ -382,9 +387,16 @@ def timed(step, args, world, ctx):
 def kernel_tables(step, args, ctx, config: str):
     """`roofline` from the timed steps' launch events (read before this is
     called: ctx.kernel_timing() right after timed()) and the `kernels` table
-    from PROFILED_STEPS more steps with every launch timed."""
+    from PROFILED_STEPS more steps with every launch timed (--full only: a
+    plain run gets no `kernels` table and runs no further step)."""
     kt_timed = ctx.kernel_timing()
     _, roofline = roofline_of(kt_timed, args.steps, config)
+    if not args.full:
+        if roofline:
+            roofline["timed_in"] = ("the timed steps (every launch timed)"
+                                    if os.environ.get("RK_BENCH_ALLPROF")
+                                    else "the timed steps (this kernel's launches only)")
+        return None, roofline
     ctx.set_profiling(True)
     ctx.reset_phases()
     for _ in range(PROFILED_STEPS):
@@ -408,6 +420,47 @@ def upload(f, dev):
             torch.from_numpy(f.y_start.view(np.int64)).to(dev),
             torch.from_numpy(f.length.view(np.int64)).to(dev),
             torch.from_numpy(f.strand).to(dev))
+
+
+# --dump-outputs: at most this many output rows over all ranks (28 B per row
+# as written: three float64 columns and one float32 -> 42 MB)
+DUMP_ROWS = 1_500_000
+
+
+def dump_rows(n_out: int, rank: int, world: int) -> np.ndarray:
+    """The output rows --dump-outputs writes: all of them when they fit this
+    rank's share of DUMP_ROWS, else a fixed seeded sample (sorted, distinct)."""
+    k = DUMP_ROWS // world
+    if n_out <= k:
+        return np.arange(n_out, dtype=np.int64)
+    return np.unique(np.random.default_rng(20240 + rank).integers(0, n_out, k, dtype=np.int64))
+
+
+def dump_outputs(dirpath: str, rank: int, world: int, n_out: int, n_groups: int,
+                 order, gid, rep) -> None:
+    """What the last timed step returned to its caller, as DIR/<name>.npy
+    (`_rank<r>` before `.npy` at N > 1): `counts` (n_out, n_groups),
+    `rows` (the output rows kept, see dump_rows) and, at those rows,
+    `out_order`, `gid` (uint32 values as float64, exact) and `repval`
+    (float32).  order / gid / rep: torch tensors (any device) or numpy arrays
+    whose first n_out rows are the result."""
+    os.makedirs(dirpath, exist_ok=True)
+    rows = dump_rows(n_out, rank, world)
+
+    def take(a, bits):
+        if isinstance(a, torch.Tensor):
+            a = a[:n_out][torch.from_numpy(rows).to(a.device)].cpu().numpy()
+        else:
+            a = np.asarray(a)[:n_out][rows]
+        return a.view(bits) if a.dtype.itemsize == np.dtype(bits).itemsize else a.astype(bits)
+
+    sfx = f"_rank{rank}" if world > 1 else ""
+    for name, arr in (("counts", np.array([n_out, n_groups], dtype=np.float64)),
+                      ("rows", rows.astype(np.float64)),
+                      ("out_order", take(order, np.uint32).astype(np.float64)),
+                      ("gid", take(gid, np.uint32).astype(np.float64)),
+                      ("repval", take(rep, np.uint8).astype(np.float32))):
+        np.save(os.path.join(dirpath, f"{name}{sfx}.npy"), arr)
 
 
 def config_seed(name: str) -> int:
@@ -501,16 +554,21 @@ def bench_sharded(args, cfg, rank, world, local, dev, ctx) -> dict:
     log(f"sharded: {args.steps} timed steps in {dt:.3f} s")
     frags_total, dt_max = aggregate(world, n, dt)
     # the timed steps' result, before any further step runs
-    share = rk.shard_copy(ctx, out)
+    share = rk.shard_copy(ctx, out) if args.full or args.dump_outputs else None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, world, len(share.out_order), out.n_groups,
+                     share.out_order, share.gid, share.repval)
     st = rk.shard_stats(ctx)
     sent = allsum(world, float(st["bytes_sent"]))
     kernels, roofline = kernel_tables(step, args, ctx, f"{args.config}-sharded-x{world}")
     comm.close()
-    whole = gather_result(world, rank, out.out_offset, share.out_order, share.gid, share.repval,
-                          out.n_out_total)
-    log("sharded: result gathered")
+    whole = None
+    if args.full:
+        whole = gather_result(world, rank, out.out_offset, share.out_order, share.gid,
+                              share.repval, out.n_out_total)
+        log("sharded: result gathered")
     parity = None
-    if rank == 0:
+    if rank == 0 and args.full:
         digest = arrays_sha256(*whole)
         e = large_entry(cfg)
         pinned = (one_set and e is not None
@@ -589,8 +647,27 @@ def host_legs(ctx, x, y, ln, s, L, args) -> dict:
     return out
 
 
-def bench_single(args, cfg, rank, world, dev, ctx) -> dict:
-    """rk_classify_device on this rank's own fragment set (inputs resident in HBM)."""
+def single_parity(cfg, rank, n, L, n_out, order, gid, rep):
+    """The result of the timed steps, digested (tests/test_large_configs.py's
+    definition) and compared with the REFERENCE's result for this input where
+    tests/golden/large_hashes.json pins it (cfg3: seed 3 = rank 0's set)."""
+    digest = arrays_sha256(order[:n_out].cpu().numpy().view(np.uint32),
+                           gid[:n_out].cpu().numpy().view(np.uint32), rep[:n_out].cpu().numpy())
+    e = large_entry(cfg)
+    pinned = (e is not None and e.get("synth", {}).get("seed") == rank_seed(rank)
+              and e["synth"].get("n") == n and e["synth"].get("genome_len") == L
+              and not cfg.get("synth"))
+    parity = {"result_sha256": digest,
+              "matches_reference_digest": (digest == e["result_sha256"]) if pinned else None,
+              "pinned_by": ("tests/golden/large_hashes.json (the reference's output for this "
+                            "input, reproduced byte-exact as CSV by test_cfg3_reference_csv)"
+                            if pinned else "no reference digest for this input")}
+    return parity, digest
+
+
+def bench_single(args, cfg, rank, world, dev, ctx, dump: bool = False) -> dict:
+    """rk_classify_device on this rank's own fragment set (inputs resident in HBM).
+    dump: this leg is the run's value, so --dump-outputs writes its result."""
     n, L = cfg["n"], cfg["genome_len"]
     f = rk.synth(n, L, seed=rank_seed(rank), **cfg.get("synth", {}))  # own set per rank
     x, y, ln, s = upload(f, dev)
@@ -598,7 +675,8 @@ def bench_single(args, cfg, rank, world, dev, ctx) -> dict:
     rep = torch.empty(n, dtype=torch.uint8, device=dev)
     order = torch.empty(n, dtype=torch.int32, device=dev)
     # the host arrays stay for the same-input CPU baseline (rank 0, one GPU)
-    keep_host = rank == 0 and world == 1 and not args.no_cpu and n <= 50_000_000
+    keep_host = (args.full and rank == 0 and world == 1 and not args.no_cpu
+                 and n <= 50_000_000)
     if not keep_host:
         del f
 
@@ -612,29 +690,19 @@ def bench_single(args, cfg, rank, world, dev, ctx) -> dict:
     frags_total, dt_max = aggregate(world, n, dt)
     phases = ctx.phases()
     st = ctx.stats()
+    if dump and args.dump_outputs:  # the last timed step's result, before any further step
+        dump_outputs(args.dump_outputs, rank, world, n_out, n_groups, order, gid, rep)
     kernels, roofline = kernel_tables(step, args, ctx, args.config)
 
     # host-to-host rate (host SoA in, host results out: rk_classify), reported
     # beside value, never as it (SURVEY.md §8d's PCIe-inclusive timed region)
     host = None
-    if rank == 0 and args.config in ("cfg2", "cfg3", "cfg4"):  # cfg5: no HBM for a 2nd copy
+    if args.full and rank == 0 and args.config in ("cfg2", "cfg3", "cfg4"):  # cfg5: no HBM for a 2nd copy
         host = host_legs(ctx, x, y, ln, s, L, args)
     per_step = {k: v[0] / max(1, v[1]) for k, v in phases.items()}
     value = frags_total * args.steps / dt_max
-    # the result of the timed steps, digested (tests/test_large_configs.py's
-    # definition) and compared with the REFERENCE's result for this input where
-    # tests/golden/large_hashes.json pins it (cfg3: seed 3 = rank 0's set)
-    digest = arrays_sha256(order[:n_out].cpu().numpy().view(np.uint32),
-                           gid[:n_out].cpu().numpy().view(np.uint32), rep[:n_out].cpu().numpy())
-    e = large_entry(cfg)
-    pinned = (e is not None and e.get("synth", {}).get("seed") == rank_seed(rank)
-              and e["synth"].get("n") == n and e["synth"].get("genome_len") == L
-              and not cfg.get("synth"))
-    parity = {"result_sha256": digest,
-              "matches_reference_digest": (digest == e["result_sha256"]) if pinned else None,
-              "pinned_by": ("tests/golden/large_hashes.json (the reference's output for this "
-                            "input, reproduced byte-exact as CSV by test_cfg3_reference_csv)"
-                            if pinned else "no reference digest for this input")}
+    parity, digest = (single_parity(cfg, rank, n, L, n_out, order, gid, rep) if args.full
+                      else (None, None))
     same_input = (f, L, digest) if keep_host else None
     line = {
         "metric": METRIC,
@@ -664,6 +732,9 @@ def bench_single(args, cfg, rank, world, dev, ctx) -> dict:
         "host_to_host": host,
         "parity": parity,
     }
+    if not args.full:  # not measured in a plain run
+        for k in ("kernels", "host_to_host_fragments_per_s", "host_to_host", "parity"):
+            del line[k]
     return line, same_input
 
 
@@ -673,7 +744,15 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="cfg3", choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what takes runs of its own: the "
+                         "per-kernel table, the host-to-host legs, the result digest against "
+                         "the reference's, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy "
+                         "(a fixed seeded sample of the output rows, see dump_outputs)")
+    ap.add_argument("--no-cpu", action="store_true",
+                    help="with --full: skip the CPU baseline leg")
     ap.add_argument("--len-ratio", type=float, default=0.3)
     ap.add_argument("--pos-ratio", type=float, default=0.3)
     ap.add_argument("--mode", default="auto", choices=["auto", "replicas", "sharded"],
@@ -714,7 +793,8 @@ def main():
     if args.mode == "sharded":
         line = sharded_line(bench_sharded(args, cfg, rank, world, local, dev, ctx))
     else:
-        line, same_input = bench_single(args, cfg, rank, world, dev, ctx)
+        line, same_input = bench_single(args, cfg, rank, world, dev, ctx,
+                                        dump=world == 1 or args.mode == "replicas")
         if world > 1 and args.mode == "auto":
             # N > 1: the value is ONE comparison sharded over the GPUs (xStart/10
             # slices, RCCL exchanges); the independent replicas measured above
@@ -759,7 +839,7 @@ def main():
                 line["replicas"] = replicas
     if rank != 0:
         return
-    if not args.no_cpu:
+    if args.full and not args.no_cpu:
         # (N > 1: rank 0's host, the reference sample alone -- the arrays of
         # the whole set are not kept for the restatement there)
         log("cpu baseline")

@@ -49,18 +49,18 @@ suite)
   timeout -k 10 1100 python3 -u -m pytest tests -m gpu -x -v --timeout 600 --timeout-method thread > $O/gpu_tests.log 2>&1 || exit 2
   ;;
 bench)
-  bench bench --gpus 1 --steps 20 --warmup 5 || exit 1
+  bench bench --gpus 1 --full --steps 20 --warmup 5 || exit 1
   ;;
 refresh)
-  bench bench --gpus 1 --steps 20 --warmup 5 || exit 1
-  timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o p -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu > $O/prof.log 2>&1 || exit 2
+  bench bench --gpus 1 --full --steps 20 --warmup 5 || exit 1
+  timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o p -- python3 bench.py --gpus 1 --full --steps 20 --warmup 5 --no-cpu > $O/prof.log 2>&1 || exit 2
   bash tools/pmc_run.sh $O/pmc --no-cpu --steps 3 --warmup 1 || exit 3
-  bench bench_cfg5 --gpus 1 --config cfg5 --steps 3 --warmup 1 --no-cpu || exit 4
+  bench bench_cfg5 --gpus 1 --config cfg5 --full --steps 3 --warmup 1 --no-cpu || exit 4
   timeout -k 10 600 python3 tools/pairs_bench.py > $O/pairs.json 2> $O/pairs.err || exit 5
   ;;
 cfg5)
   timeout -k 10 600 python3 -u tools/cfg5_check.py --out $O/cfg5_check.json > $O/cfg5_check.log 2>&1 || exit 1
-  bench bench_cfg5 --config cfg5 --no-cpu --steps 3 --warmup 1 || exit 2
+  bench bench_cfg5 --config cfg5 --full --no-cpu --steps 3 --warmup 1 || exit 2
   ;;
 longprof)  # the long-run walk's counters (RK_SWEEP_PROF build under tools/mb/prof)
   RK_LIB=tools/mb/prof/librepkiller_amd.so bench long_cfg5 --config cfg5 --no-cpu --steps 1 --warmup 0 || exit 1
@@ -127,8 +127,8 @@ parity)  # the record / generic pipelines against the oracle and the fixtures
 check)  # parity + sharded tests + the cfg5q digests (one device, 8 ranks) + cfg5 bench + 2-rank rehearsal
   timeout -k 10 900 python3 -u -m pytest tests/test_gpu_parity.py tests/test_sharded.py -x -v --timeout 300 --timeout-method thread > $O/parity.log 2>&1 || exit 1
   timeout -k 10 900 python3 -u -m pytest tests/test_large_configs.py -x -v -k cfg5q --timeout 600 --timeout-method thread > $O/cfg5q.log 2>&1 || exit 2
-  bench bench_cfg5 --config cfg5 --no-cpu --steps 3 --warmup 1 || exit 3
-  RK_BENCH_SAME_GPU=1 timeout -k 10 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29612 bench.py --gpus 2 --comm host --steps 2 --warmup 1 --sharded-timeout 500 > $O/host2.json 2> $O/host2.err || exit 4
+  bench bench_cfg5 --config cfg5 --full --no-cpu --steps 3 --warmup 1 || exit 3
+  RK_BENCH_SAME_GPU=1 timeout -k 10 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29612 bench.py --gpus 2 --comm host --full --steps 2 --warmup 1 --sharded-timeout 500 > $O/host2.json 2> $O/host2.err || exit 4
   ;;
 ablib)
   timeout -k 10 600 python3 -u -m pytest tests/test_gpu_parity.py -x -q --timeout 300 --timeout-method thread > $O/parity.log 2>&1 || exit 1
@@ -197,21 +197,21 @@ shard)
   if [ "$1" = large ]; then
     timeout -k 10 900 python3 -u -m pytest tests/test_large_configs.py -x -q -k sharded --timeout 600 --timeout-method thread > $O/large_tests.log 2>&1 || exit 2
   fi
-  bench sharded_w1 --mode sharded --steps 20 --warmup 5 --no-cpu || exit 3
+  bench sharded_w1 --mode sharded --full --steps 20 --warmup 5 --no-cpu || exit 3
   ;;
 rehearse)  # ARGS: world sizes (default 2 4); cfg3's one 50M set strong-scaled, parity gathered
   for W in ${@:-2 4}; do
-    RK_BENCH_SAME_GPU=1 timeout -k 10 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node $W --master-addr 127.0.0.1 --master-port $((29610 + W)) bench.py --gpus $W --comm host --steps 2 --warmup 1 --sharded-timeout 500 > $O/host$W.json 2> $O/host$W.err || exit 1
+    RK_BENCH_SAME_GPU=1 timeout -k 10 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node $W --master-addr 127.0.0.1 --master-port $((29610 + W)) bench.py --gpus $W --comm host --full --steps 2 --warmup 1 --sharded-timeout 500 > $O/host$W.json 2> $O/host$W.err || exit 1
   done
-  bench sharded_w1 --mode sharded --no-cpu --steps 5 --warmup 2 || exit 3
+  bench sharded_w1 --mode sharded --full --no-cpu --steps 5 --warmup 2 || exit 3
   ;;
 fast)  # the sharded fast path: its tests, the whole sharded suite, the 2- and 4-rank rehearsals, world 1
   timeout -k 10 900 python3 -u -m pytest tests/test_sharded.py -x -v -k "fast" --timeout 300 --timeout-method thread > $O/fast_tests.log 2>&1 || exit 1
   timeout -k 10 1100 python3 -u -m pytest tests/test_sharded.py -x -v --timeout 300 --timeout-method thread > $O/sharded_tests.log 2>&1 || exit 2
   for W in 2 4; do
-    RK_BENCH_SAME_GPU=1 timeout -k 10 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node $W --master-addr 127.0.0.1 --master-port $((29610 + W)) bench.py --gpus $W --comm host --steps 2 --warmup 1 --sharded-timeout 500 > $O/host$W.json 2> $O/host$W.err || exit 3
+    RK_BENCH_SAME_GPU=1 timeout -k 10 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node $W --master-addr 127.0.0.1 --master-port $((29610 + W)) bench.py --gpus $W --comm host --full --steps 2 --warmup 1 --sharded-timeout 500 > $O/host$W.json 2> $O/host$W.err || exit 3
   done
-  bench sharded_w1 --mode sharded --no-cpu --steps 20 --warmup 5 || exit 4
+  bench sharded_w1 --mode sharded --full --no-cpu --steps 20 --warmup 5 || exit 4
   ;;
 io)  # the whole file path at cfg3 (CSV in -> classify -> CSV out) against the reference on the same file
   T=/tmp
@@ -220,18 +220,18 @@ io)  # the whole file path at cfg3 (CSV in -> classify -> CSV out) against the r
   timeout -k 10 1100 python3 -u tools/io_bench.py --tmp $T > $O/io_bench.json 2> $O/io_bench.err || exit 1
   ;;
 rehearse_rccl)  # RCCL refuses two ranks on one GPU: value null with the error
-  RK_BENCH_SAME_GPU=1 timeout -k 10 300 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29612 bench.py --gpus 2 --config cfg2 --steps 3 --warmup 1 --sharded-timeout 60 > $O/rccl2.json 2> $O/rccl2.err
+  RK_BENCH_SAME_GPU=1 timeout -k 10 300 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29612 bench.py --gpus 2 --config cfg2 --full --steps 3 --warmup 1 --sharded-timeout 60 > $O/rccl2.json 2> $O/rccl2.err
   echo "rccl2 exit $?" > $O/rccl2.rc
   ;;
 serial)
-  RK_ONE_STREAM=1 bench cfg3 --no-cpu || exit 1
-  RK_ONE_STREAM=1 bench cfg5 --config cfg5 --no-cpu --steps 2 --warmup 1 || exit 2
+  RK_ONE_STREAM=1 bench cfg3 --full --no-cpu || exit 1
+  RK_ONE_STREAM=1 bench cfg5 --config cfg5 --full --no-cpu --steps 2 --warmup 1 || exit 2
   ;;
 pmc5)
   bash tools/pmc_run.sh $O/pmc5 --config cfg5 --no-cpu --steps 1 --warmup 1 || exit 1
   ;;
 shprof)
-  timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/shprof -o p -- python3 bench.py --mode sharded --no-cpu --steps 10 --warmup 3 > $O/shprof.json 2> $O/shprof.err || exit 1
+  timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/shprof -o p -- python3 bench.py --mode sharded --full --no-cpu --steps 10 --warmup 3 > $O/shprof.json 2> $O/shprof.err || exit 1
   ;;
 *)
   echo "unknown task $TASK" >&2
