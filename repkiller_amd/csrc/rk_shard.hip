@@ -1154,9 +1154,124 @@ std::vector<uint64_t> global_hist(Shard &S, const Op &op, uint32_t n,
   return g;
 }
 
+// the histogram's count between bounds q and q + 1 (the bounds lie on bins)
+template <class T>
+uint64_t bins_in(const T *h, const Bounds &B, uint32_t q, uint32_t shift) {
+  const uint64_t unit = 1ull << shift;
+  const uint64_t b0 = (B.b[q] + unit - 1) >> shift, b1 = (B.b[q + 1] + unit - 1) >> shift;
+  uint64_t c = 0;
+  for (uint64_t b = b0; b < b1 && b < NBINS; ++b) c += h[b];
+  return c;
+}
+
+// every rank's slice size -> the slices' processing-index bounds (this rank's
+// first index: b[me])
+Bounds slice_offsets(const std::vector<uint64_t> &mall) {
+  Bounds slices{};
+  slices.P = (uint32_t)mall.size();
+  for (uint32_t q = 0, acc = 0; q <= MAXP; ++q) {
+    slices.b[q] = acc;
+    if (q < slices.P) acc += (uint32_t)mall[q];
+  }
+  return slices;
+}
+
+// the lead-in start bucket of every slice (~0: an empty slice has none)
+void lead_in_thresholds(uint64_t thr[MAXP], const std::vector<uint64_t> &mall,
+                        const Bounds &slice_keys, uint64_t H) {
+  for (uint32_t g = 0; g < MAXP; ++g) {
+    thr[g] = ~0ull;
+    if (g < mall.size() && mall[g]) {
+      const uint64_t bmin = slice_keys.b[g] / 10;  // xStart >= 10*key, centre >= xStart
+      thr[g] = bmin >= 1 + H ? bmin - 1 - H : 0;
+    }
+  }
+}
+
+// the call's result: this rank's share of the output among every rank's
+void set_result(rk_shard_result *out, uint32_t *oord, uint32_t *ogid, uint8_t *orep, uint32_t mr,
+                const std::vector<uint64_t> &oall, uint32_t me, uint64_t Gtot) {
+  uint64_t ooff = 0, otot = 0;
+  for (uint32_t q = 0; q < oall.size(); ++q) otot += oall[q], ooff += q < me ? oall[q] : 0;
+  out->out_order = oord;
+  out->gid = ogid;
+  out->repval = orep;
+  out->n_out = mr;
+  out->out_offset = ooff;
+  out->n_out_total = otot;
+  out->n_groups = Gtot;
+}
+
 double ms_since(std::chrono::steady_clock::time_point t0) {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
+
+// A call's geometry, built once (shard_geom) for all three drivers.
+struct Geom {
+  uint64_t H;                    // lead-in buckets
+  uint64_t vsize, max_x, max_y;  // FragmentsDatabase.cpp:84, SequenceOcupationList.cpp:4
+  uint32_t nbx, nby;
+  uint32_t drop;           // the never-iterated last bucket
+  uint32_t shift, yshift;  // histogram bin shifts of the xStart/10 keys and the Y buckets
+};
+
+Geom shard_geom(const rk_params &p, int32_t lead_in) {
+  Geom g{};
+  g.H = lead_in < 0 ? 2 : (uint64_t)lead_in;
+  const uint64_t len_x = p.len_x_hdr + 1, len_y = p.len_y_hdr + 1;  // FragmentsDatabase.cpp:62,65
+  g.vsize = 1 + len_x / 10;
+  g.max_x = len_x / 100, g.max_y = len_y / 100;
+  g.nbx = (uint32_t)(g.max_x + 1), g.nby = (uint32_t)(g.max_y + 1);
+  g.drop = (uint32_t)(g.vsize - 1);
+  g.shift = bin_shift(g.drop), g.yshift = bin_shift(g.nby);
+  return g;
+}
+
+// The record drivers' per-call state (rk_shard_nw.h's stages fill it; a retry
+// on the careful driver starts from a fresh one).
+struct RecState : Geom {
+  rk_params p;
+  const rk_frags_soa *in;
+  Frags f;
+  uint32_t nl;
+  uint64_t row_base = 0;
+  // the digit plans; one: the one-rank route, the rows read once as on one
+  // device (in_place: no row dropped, the order sort reads the rows themselves)
+  NwDigits ad, yd;
+  NwOrderPlan op1;
+  bool one, in_place = false, y_early;
+  // slice facts
+  Bounds slice_keys{}, slices{};
+  std::vector<uint64_t> mall;  // every rank's slice size
+  uint64_t kept = 0;           // this rank's kept rows
+  uint32_t m = 0, poff = 0, maxlen = 0;
+  uint64_t span = 0;
+  // Y facts
+  Bounds yb{};
+  uint64_t ylo = 0, yhi = 0;
+  uint32_t ny = 0;
+  // X facts: the last X solve's halo and entry count
+  uint32_t Gfin = 0, mx = 0;
+  // device buffers from the pool
+  uint32_t *ahist = nullptr, *yhist = nullptr, *ehist = nullptr;  // order / Y / member digits
+  uint4 *srows = nullptr, *Ra = nullptr, *yown = nullptr;
+  NwChunkCounts own_cc{};
+  bool own_counts = false;
+  const uint3 *yr = nullptr;
+  uint8_t *ycode = nullptr, *ystate = nullptr, *yused = nullptr;
+  uint32_t *ywin = nullptr, *par_l = nullptr, *ystat = nullptr, *ybits = nullptr;
+  uint4 *yA = nullptr, *yB = nullptr;
+  Csr cy{};
+  uint32_t *xg = nullptr;
+  uint8_t *xused = nullptr;
+  // member order
+  uint32_t mr = 0, g0 = 0, Gl = 0;
+  uint32_t *ogid = nullptr, *oord = nullptr, *sgid = nullptr, *mrow = nullptr, *otag = nullptr,
+           *goffs = nullptr, *tag = nullptr;
+  uint8_t *orep = nullptr;
+  uint64_t *reckey = nullptr;
+  void *gsort = nullptr;
+};
 
 // One resolved occupancy axis over `n` entries (entry i's record in rec, its
 // bucket key in key).  X: xres = the Y records (winner word), Y: xres null.
@@ -1298,49 +1413,122 @@ void verify_y_halo(Shard &S, RelOp relop, const uint8_t *ycode, uint8_t *ystate,
   }
 }
 
-// Roots and gids of both drivers: parents (own X winners in xg, the Y winners
-// of own X misses received in prr) -> slice-local parent chains compressed by
-// pointer jumping, cross-slice links by request/response rounds, gid = global
-// rank of the root among new groups.  Returns the gid of every own entry
-// (processing order); *Gtot = the number of groups.
+// The slice's root buffers and its local roots (every driver): parents (own X
+// winners in xg; the Y winners of own X misses in place or received in prr)
+// -> slice-local chains, compressed by compress(jp, junk) -- jump_round with a
+// readback per round, or jump_listed with none -- and the roots' ranks.
+struct RootBufs {
+  uint32_t *lpar, *ext, *isroot, *lrank, *junk, *lab, *cur;
+};
+RootBufs root_buffers(Shard &S, uint32_t m) {
+  RootBufs b{};
+  b.lpar = S.take<uint32_t>(SL_LPAR, m + 1);
+  b.ext = S.take<uint32_t>(SL_EXT, m + 1);
+  b.isroot = S.take<uint32_t>(SL_ISROOT, m + 2);
+  b.lrank = S.take<uint32_t>(SL_LRANK, m + 2);
+  b.junk = S.take<uint32_t>(SL_JUNK, m + 1);
+  b.lab = S.take<uint32_t>(SL_LAB, m + 1);
+  b.cur = S.take<uint32_t>(SL_CUR, m + 1);
+  return b;
+}
+template <class Compress>
+void local_roots(Shard &S, const RootBufs &b, uint32_t *xg, const ParRec *prr, uint32_t npar,
+                 uint32_t m, uint32_t poff, Compress &&compress) {
+  if (!m) return;
+  if (npar) {
+    kt_begin(S.st, KID_SHARD_AUX);
+    k_par_scatter<<<grid_for(npar, 256), 256, 0, S.st>>>(prr, npar, poff, m, xg, S.ctrl);
+    kt_end(S.st, KID_SHARD_AUX, 0.0);
+  }
+  kt_begin(S.st, KID_SHARD_AUX);
+  k_local_par<<<grid_for(m, 256), 256, 0, S.st>>>(xg, m, poff, b.lpar, b.ext, b.isroot, S.ctrl);
+  kt_end(S.st, KID_SHARD_AUX, 0.0);
+  S.launched("parents");
+  Proc jp{};
+  jp.par = b.lpar;
+  compress(jp, b.junk);
+  exclusive_scan_u32(b.isroot, b.lrank, (size_t)m + 1, S.scan_scratch(SL_SCAN, m + 1), S.st);
+}
+
+// One request/response round of the cross-slice links (every driver), over
+// the planned requests pp: they go to the owners of their targets through ex
+// (from: the requests every peer sends here), the owners answer with their
+// current knowledge, and the answers are applied.  report(rrc): this rank's
+// status before the response all-to-all -- an agreement point (both buffers
+// are sized by skewed counts and the launch can fail on one rank alone), or
+// the sticky status of a stage that runs without agreement points.
+template <class Ex, class Report>
+void request_round(Shard &S, const RootBufs &b, const Bounds &slices, uint32_t m, uint32_t poff,
+                   const PartPlan &pp, const Ex &ex, const uint64_t *from, Report &&report,
+                   bool apply_empty) {
+  ReqOp rq{b.lpar, b.lab, b.cur, slices, nullptr, nullptr};
+  rq.req = S.take<uint32_t>(SL_REQ, pp.total + 1);
+  rq.src = S.take<uint32_t>(SL_SRC, pp.total + 1);
+  S.emit(rq, pp);
+  uint32_t nq = 0;
+  const uint32_t *rqs = ex(rq.req, pp, SL_RQ, &nq);
+  uint2 *resp = nullptr, *back = nullptr;
+  int rrc = RK_OK;
+  try {
+    resp = S.take<uint2>(SL_RESP, nq + 1);
+    back = S.take<uint2>(SL_BACK, pp.total + 1);
+    if (fault_here(S.ctx, "k_respond")) throw (int)RK_E_NOMEM;
+    if (nq) {
+      k_respond<<<grid_for(nq, 256), 256, 0, S.st>>>(rqs, nq, poff, m, b.lpar, b.lab, b.cur, resp,
+                                                      S.ctrl);
+      S.launched("k_respond");
+    }
+  } catch (int code) {
+    rrc = code;
+  }
+  report(rrc);
+  uint64_t sb[MAXP], rb[MAXP];
+  for (uint32_t q = 0; q < S.P; ++q) sb[q] = from[q] * sizeof(uint2), rb[q] = pp.cnt[q] * sizeof(uint2);
+  S.run_a2a(resp, sb, back, rb);
+  if (pp.total || apply_empty) {  // (the careful rounds launch it on a rank without requests too)
+    k_apply<<<grid_for((uint32_t)pp.total, 256), 256, 0, S.st>>>(back, rq.src, (uint32_t)pp.total,
+                                                                  b.lab, b.cur);
+    S.launched("k_apply");
+  }
+}
+
+// an exchange sized by Shard::exchange's count gather, with its agreement
+// (from: filled with the per-source counts)
+struct CountedExchange {
+  Shard &S;
+  uint64_t *from = nullptr;
+  template <class T>
+  T *operator()(const T *send, const PartPlan &pp, int slot, uint32_t *nrecv) const {
+    return S.exchange<T>(send, pp, slot, nrecv, from);
+  }
+};
+
+// Roots and gids of the generic and the careful record driver: parents (own X
+// winners in xg, the Y winners of own X misses received in prr) -> slice-local
+// parent chains compressed by pointer jumping, cross-slice links by
+// request/response rounds, gid = global rank of the root among new groups.
+// Returns the gid of every own entry (processing order); *Gtot = the number
+// of groups.
 const uint32_t *resolve_roots(Shard &S, uint32_t *xg, const ParRec *prr, uint32_t npar,
                               uint32_t m, uint32_t poff, const Bounds &slices, uint64_t *Gtot_out) {
   rk_ctx *ctx = S.ctx;
   rk_shard_stats &ss = ctx->shard_stats;
   const uint32_t P = S.P, me = S.me;
   PartPlan pp;
-  uint32_t *parg = xg;  // X winners; the X misses' Y winners are scattered in
-  uint32_t *lpar = S.take<uint32_t>(SL_LPAR, m + 1);
-  uint32_t *ext = S.take<uint32_t>(SL_EXT, m + 1);
-  uint32_t *isroot = S.take<uint32_t>(SL_ISROOT, m + 2);
-  uint32_t *lrank = S.take<uint32_t>(SL_LRANK, m + 2);
-  uint32_t *junk = S.take<uint32_t>(SL_JUNK, m + 1);
-  uint32_t *lab = S.take<uint32_t>(SL_LAB, m + 1);
-  uint32_t *cur = S.take<uint32_t>(SL_CUR, m + 1);
-  if (m) {
-    if (npar) {
-      kt_begin(S.st, KID_SHARD_AUX);
-      k_par_scatter<<<grid_for(npar, 256), 256, 0, S.st>>>(prr, npar, poff, m, parg, S.ctrl);
-      kt_end(S.st, KID_SHARD_AUX, 0.0);
-    }
-    kt_begin(S.st, KID_SHARD_AUX);
-    k_local_par<<<grid_for(m, 256), 256, 0, S.st>>>(parg, m, poff, lpar, ext, isroot, S.ctrl);
-    kt_end(S.st, KID_SHARD_AUX, 0.0);
-    S.launched("parents");
-    Proc jp{};
-    jp.par = lpar;
+  const RootBufs b = root_buffers(S, m);
+  uint32_t *lpar = b.lpar, *lrank = b.lrank, *junk = b.junk;
+  local_roots(S, b, xg, prr, npar, m, poff, [&](Proc jp, uint32_t *isnew) {
     for (uint32_t rounds = 0;; ++rounds) {
       if (rounds > 64) {
         ctx->err = "pointer jumping did not converge";
         throw RK_E_INTERNAL;
       }
       S.zero(S.ctrl + 3, 4);
-      jump_round(jp, m, S.ctrl + 3, rounds == 0 ? junk : nullptr, S.ctrl, S.st);
+      jump_round(jp, m, S.ctrl + 3, rounds == 0 ? isnew : nullptr, S.ctrl, S.st);
       S.launched("jump_round");
       if (!S.read1(S.ctrl + 3)) break;
     }
-    exclusive_scan_u32(isroot, lrank, (size_t)m + 1, S.scan_scratch(SL_SCAN, m + 1), S.st);
-  }
+  });
   // the error bits, the root count and the cross-slice link flag: one readback
   uint32_t nroots = 0, xlink = 0, ebits = 0;
   if (m) {
@@ -1379,54 +1567,27 @@ const uint32_t *resolve_roots(Shard &S, uint32_t *xg, const ParRec *prr, uint32_
   }
   if (m) {
     kt_begin(S.st, KID_SHARD_AUX);
-    k_init_labels<<<grid_for(m, 256), 256, 0, S.st>>>(lpar, ext, lrank, (uint32_t)goff, m, lab,
-                                                        cur);
+    k_init_labels<<<grid_for(m, 256), 256, 0, S.st>>>(lpar, b.ext, lrank, (uint32_t)goff, m,
+                                                        b.lab, b.cur);
     kt_end(S.st, KID_SHARD_AUX, 0.0);
     S.launched("k_init_labels");
   }
   for (;;) {  // cross-slice links: request/response rounds (the owner answers
               // with its current knowledge, so chains halve every round)
-    ReqOp rq{lpar, lab, cur, slices, nullptr, nullptr};
-    S.plan(rq, m, pp);
+    S.plan(ReqOp{lpar, b.lab, b.cur, slices, nullptr, nullptr}, m, pp);
     if (S.sum_any(pp.total) == 0) break;
     if (++ss.root_rounds > 64) {
       ctx->err = "cross-slice root resolution did not converge";
       throw RK_E_INTERNAL;
     }
-    rq.req = S.take<uint32_t>(SL_REQ, pp.total + 1);
-    rq.src = S.take<uint32_t>(SL_SRC, pp.total + 1);
-    S.emit(rq, pp);
-    uint32_t nq = 0;
     uint64_t from[MAXP];
-    const uint32_t *rqs = S.exchange<uint32_t>(rq.req, pp, SL_RQ, &nq, from);
-    // the response all-to-all needs its own agreement point: both buffers are
-    // sized by skewed counts and the launch can fail on one rank alone
-    uint2 *resp = nullptr, *back = nullptr;
-    int rrc = RK_OK;
-    try {
-      resp = S.take<uint2>(SL_RESP, nq + 1);
-      back = S.take<uint2>(SL_BACK, pp.total + 1);
-      if (fault_here(ctx, "k_respond")) throw (int)RK_E_NOMEM;
-      if (nq) {
-        k_respond<<<grid_for(nq, 256), 256, 0, S.st>>>(rqs, nq, poff, m, lpar, lab, cur, resp,
-                                                        S.ctrl);
-        S.launched("k_respond");
-      }
-    } catch (int code) {
-      rrc = code;
-    }
-    S.agree(rrc);
-    uint64_t sb[MAXP], rb[MAXP];
-    for (uint32_t q = 0; q < P; ++q) sb[q] = from[q] * sizeof(uint2), rb[q] = pp.cnt[q] * sizeof(uint2);
-    S.run_a2a(resp, sb, back, rb);
-    k_apply<<<grid_for((uint32_t)pp.total, 256), 256, 0, S.st>>>(back, rq.src, (uint32_t)pp.total,
-                                                                  lab, cur);
-    S.launched("k_apply");
+    request_round(S, b, slices, m, poff, pp, CountedExchange{S, from}, from,
+                  [&](int rrc) { S.agree(rrc); }, true);
   }
   uint32_t *gid_own = junk;  // the jump's scratch is free again
   if (m) {
     kt_begin(S.st, KID_SHARD_AUX);
-    k_final_gid<<<grid_for(m, 256), 256, 0, S.st>>>(lpar, lab, m, gid_own, S.ctrl);
+    k_final_gid<<<grid_for(m, 256), 256, 0, S.st>>>(lpar, b.lab, m, gid_own, S.ctrl);
     kt_end(S.st, KID_SHARD_AUX, 0.0);
     S.launched("k_final_gid");
   }
@@ -1465,11 +1626,10 @@ int classify_sharded_impl(Shard &S, const rk_frags_soa *in, const rk_params *prm
   rk_shard_stats &ss = ctx->shard_stats;
   std::memset(&ss, 0, sizeof ss);
   const uint32_t P = S.P, me = S.me;
-  const uint64_t H = lead_in < 0 ? 2 : (uint64_t)lead_in;
   const rk_params p = pre ? rk_params{1000, 1000, 1, 1} : *prm;
-  const uint64_t len_x = p.len_x_hdr + 1, len_y = p.len_y_hdr + 1;  // FragmentsDatabase.cpp:62,65
-  const uint64_t vsize = 1 + len_x / 10;                             // :84
-  const uint64_t max_x = len_x / 100, max_y = len_y / 100;           // SequenceOcupationList.cpp:4
+  const Geom geo = shard_geom(p, lead_in);
+  const uint64_t H = geo.H, vsize = geo.vsize, max_x = geo.max_x, max_y = geo.max_y;
+  const uint32_t nbx = geo.nbx, nby = geo.nby, drop = geo.drop;
   // local argument checks become this rank's status in the first collective,
   // so a rank that cannot run never leaves its peers waiting
   int rc = pre;
@@ -1481,8 +1641,6 @@ int classify_sharded_impl(Shard &S, const rk_frags_soa *in, const rk_params *prm
     ctx->err = "sequence length too large for 32-bit bucket ids";
     rc = RK_E_ARG;
   }
-  const uint32_t nbx = (uint32_t)(max_x + 1), nby = (uint32_t)(max_y + 1);
-  const uint32_t drop = (uint32_t)(vsize - 1);  // the never-iterated last bucket
 
   if (!rc && ctx->profiling) {  // launch-level timing of the pipeline kernels
     ctx->kt.n = 0;
@@ -1497,23 +1655,25 @@ int classify_sharded_impl(Shard &S, const rk_frags_soa *in, const rk_params *prm
     }
   }
 
-  // the record pipeline's internals when every row of every rank packs into a
-  // 16-B record (rk_shard_nw.h); RK_SHARD_GENERIC=1 forces this driver
-  static const bool generic_only = [] {
-    const char *e = std::getenv("RK_SHARD_GENERIC");
-    return e && e[0] == '1';
-  }();
-  // the fast path (rk_shard_fast.h) unless RK_SH_FAST=0 or the round-3 Y
-  // schedule is asked for (RK_SH_YEARLY=1, the careful driver's option)
-  static const bool fast_on = [] {
-    const char *e = std::getenv("RK_SH_FAST"), *y = std::getenv("RK_SH_YEARLY");
-    return !(e && e[0] == '0') && !(y && y[0] == '1');
-  }();
+  // The driver choice; every switch is read here, once.  The record
+  // pipeline's internals when every row of every rank packs into a 16-B
+  // record (rk_shard_nw.h); RK_SHARD_GENERIC=1 forces this driver.
+  // RK_SH_YEARLY=1: the careful driver's round-3 Y schedule; RK_SH_ONE=0: the
+  // record route at world size 1 too.  The fast path (rk_shard_fast.h) unless
+  // RK_SH_FAST=0 or RK_SH_YEARLY=1.
+  static const auto env_is = [](const char *name, char v) {
+    const char *e = std::getenv(name);
+    return e && e[0] == v;
+  };
+  static const bool generic_only = env_is("RK_SHARD_GENERIC", '1');
+  static const bool y_early = env_is("RK_SH_YEARLY", '1');
+  static const bool one_on = !env_is("RK_SH_ONE", '0');
+  static const bool fast_on = !env_is("RK_SH_FAST", '0') && !y_early;
   uint64_t row_base = 0, N = 0;
   if (!generic_only && fast_on) {
     int r;
     try {
-      r = classify_sharded_fast(S, in, p, lead_in, out, rc, &N, &row_base);
+      r = classify_sharded_fast(S, geo, in, p, one_on, out, rc, &N, &row_base);
     } catch (...) {
       std::memset(ctx->sh_fp, 0, sizeof ctx->sh_fp);
       throw;
@@ -1527,7 +1687,7 @@ int classify_sharded_impl(Shard &S, const rk_frags_soa *in, const rk_params *prm
       std::memset(ctx->sh_fp, 0, sizeof ctx->sh_fp);
       ss.fast_retry = 1;
       S.zero(S.ctrl, 256 * 4);
-      r = classify_sharded_nw(S, in, p, P, me, N, row_base, lead_in, out, t0);
+      r = classify_sharded_nw(S, geo, in, p, one_on, y_early, row_base, out, t0);
       for (int a = 0; a < 2; ++a)
         ctx->sh_blind[a] = S.max_sweeps[a] > 3 ? S.max_sweeps[a] : 3u;
     }
@@ -1551,7 +1711,7 @@ int classify_sharded_impl(Shard &S, const rk_frags_soa *in, const rk_params *prm
   ss.n_in = nl;
   ss.n_total = N;
   if (!generic_only && !fast_on) {
-    const int r = classify_sharded_nw(S, in, p, P, me, N, row_base, lead_in, out, t0);
+    const int r = classify_sharded_nw(S, geo, in, p, one_on, y_early, row_base, out, t0);
     if (r != RK_SHARD_FALLBACK) {
       finish_stats(S, nl, out, t0);
       return r;
@@ -1597,15 +1757,8 @@ int classify_sharded_impl(Shard &S, const rk_frags_soa *in, const rk_params *prm
                      S.take<uint32_t>(SL_RADIX, rw), rw, S.st);
   }
   std::vector<uint64_t> mall = S.gather1<uint64_t>(m);
-  uint64_t poff64 = 0, M = 0;
-  for (uint32_t q = 0; q < P; ++q) M += mall[q], poff64 += q < me ? mall[q] : 0;
-  const uint32_t poff = (uint32_t)poff64;
-  Bounds slices{};
-  slices.P = P;
-  for (uint32_t q = 0, acc = 0; q <= MAXP; ++q) {
-    slices.b[q] = acc;
-    if (q < P) acc += (uint32_t)mall[q];
-  }
+  const Bounds slices = slice_offsets(mall);
+  const uint32_t poff = (uint32_t)slices.b[me];
   ss.n_slice = m;
   ss.ms_ingress = ms_since(t0);
 
@@ -1617,13 +1770,7 @@ int classify_sharded_impl(Shard &S, const rk_frags_soa *in, const rk_params *prm
   gop.P = P;
   gop.me = me;
   gop.poff = poff;
-  for (uint32_t g = 0; g < MAXP; ++g) {
-    gop.thr[g] = ~0ull;
-    if (g < P && mall[g]) {
-      const uint64_t bmin = slice_keys.b[g] / 10;  // xStart >= 10*key, centre >= xStart
-      gop.thr[g] = bmin >= 1 + H ? bmin - 1 - H : 0;
-    }
-  }
+  lead_in_thresholds(gop.thr, mall, slice_keys, H);
   {  // the suffix of the slice whose centres can reach a later slice's lead-in
     uint64_t thr_min = ~0ull;
     for (uint32_t g = me + 1; g < P; ++g) thr_min = gop.thr[g] < thr_min ? gop.thr[g] : thr_min;
@@ -1935,21 +2082,11 @@ int classify_sharded_impl(Shard &S, const rk_frags_soa *in, const rk_params *prm
     S.launched("member order");
   }
   std::vector<uint64_t> oall = S.gather1<uint64_t>(mr);
-  uint64_t ooff = 0, otot = 0;
-  for (uint32_t q = 0; q < P; ++q) otot += oall[q], ooff += q < me ? oall[q] : 0;
   S.hip(hipStreamSynchronize(S.st), "final sync");
   S.agree_errors();
   ss.ms_members = ms_since(tm);
-
-  out->out_order = oord;
-  out->gid = ogid;
-  out->repval = orep;
-  out->n_out = mr;
-  out->out_offset = ooff;
-  out->n_out_total = otot;
-  out->n_groups = Gtot;
+  set_result(out, oord, ogid, orep, mr, oall, me, Gtot);
   finish_stats(S, nl, out, t0);
-  (void)M;
   return RK_OK;
 }
 

@@ -7,7 +7,12 @@
 // round: ~20 host waits and ~21-24 all-gathers per call at 2-4 ranks.  Over
 // RCCL an all-gather is itself a wait, so at 8 ranks (~1.2 ms of device work
 // per rank at cfg3) the round trips would decide the time.  This driver makes
-// the same exchanges, in the same order, with the same kernels, but learns
+// the same exchanges, in the same order, with the same kernels -- it calls the
+// careful driver's stage functions (rk_shard_nw.h, rk_shard.hip), binding
+// their exchange policy to FastExchange, their resolver to the queued sweeps
+// and their chain compression to jump_listed; its own are the messages
+// below, the fingerprints, k_sh_counts, the single-shot halo comparisons, the
+// retry decisions and plan_to_msg -- but learns
 // their sizes from a few messages assembled ON THE DEVICE (histograms, count
 // matrices, flags written by the kernels that produce them) and gathered in
 // one collective with one wait each:
@@ -257,16 +262,6 @@ __global__ void k_final_gid_spec(const uint32_t *lpar, const uint32_t *lab, uint
 }
 
 // ---- host helpers --------------------------------------------------------------
-// per source rank and slice, the rows of its gathered histogram in the slice
-template <class T>
-static uint64_t bins_in(const T *h, const Bounds &B, uint32_t q, uint32_t shift) {
-  const uint64_t unit = 1ull << shift;
-  const uint64_t b0 = (B.b[q] + unit - 1) >> shift, b1 = (B.b[q + 1] + unit - 1) >> shift;
-  uint64_t c = 0;
-  for (uint64_t b = b0; b < b1 && b < NBINS; ++b) c += h[b];
-  return c;
-}
-
 // an exchange whose per-peer counts every rank knows: straight to the
 // all-to-all (known: the stage's sizes match the last completed call, no rank
 // grows a buffer), or through Shard::exchange's count gather and agreement
@@ -323,22 +318,29 @@ void plan_to_msg(Shard &S, const Op &op, uint32_t n, PartPlan &pp, uint32_t *tot
   S.launched("k_totals");
 }
 
+// the stages' exchange policy of this driver: the per-peer counts rcnt are
+// agreed, `known` is the stage's flag (see xchg)
+struct FastExchange {
+  Shard &S;
+  bool known;
+  const uint64_t *rcnt;
+  template <class T>
+  T *operator()(const T *send, const PartPlan &pp, int slot, uint32_t *nrecv) const {
+    return xchg<T>(S, known, send, pp, rcnt, slot, nrecv);
+  }
+};
+
 // ---- the driver ------------------------------------------------------------------
 // Returns RK_OK, an error, RK_SHARD_FALLBACK (a row does not pack: the generic
 // driver) or RK_SHARD_RETRY (the careful driver).  *N_out / *row_base_out:
 // every rank's rows / this rank's first global row.
-int classify_sharded_fast(Shard &S, const rk_frags_soa *in, const rk_params &p, int32_t lead_in,
-                          rk_shard_result *out, int pre, uint64_t *N_out, uint64_t *row_base_out) {
+int classify_sharded_fast(Shard &S, const Geom &geo, const rk_frags_soa *in, const rk_params &p,
+                          bool one_on, rk_shard_result *out, int pre, uint64_t *N_out,
+                          uint64_t *row_base_out) {
   rk_ctx *ctx = S.ctx;
   rk_shard_stats &ss = ctx->shard_stats;
   const uint32_t P = S.P, me = S.me;
-  const uint64_t H = lead_in < 0 ? 2 : (uint64_t)lead_in;
-  const uint64_t len_x = p.len_x_hdr + 1, len_y = p.len_y_hdr + 1;  // FragmentsDatabase.cpp:62,65
-  const uint64_t vsize = 1 + len_x / 10;                             // :84
-  const uint64_t max_x = len_x / 100, max_y = len_y / 100;           // SequenceOcupationList.cpp:4
-  const uint32_t nbx = (uint32_t)(max_x + 1), nby = (uint32_t)(max_y + 1);
-  const uint32_t drop = (uint32_t)(vsize - 1);
-  hipStream_t st = S.st, st2 = S.st2;
+  hipStream_t st = S.st;
   if (pre) {  // this rank cannot run: its status in the peers' first gather (GA)
     (void)S.status_gather(pre, nullptr, nullptr, 0);
     throw pre;
@@ -349,58 +351,37 @@ int classify_sharded_fast(Shard &S, const rk_frags_soa *in, const rk_params &p, 
   ss.fast_path = 1;
   const bool solo = P == 1;
   auto tphase = std::chrono::steady_clock::now();
+  // the sweeps queued, as many as the last careful call took; an axis left
+  // open sets F[3] (X) / F[4] (Y)
+  const auto resolve = [&](const Axis &a, const SweepScratch &sc, int axis) {
+    S.check(resolve_axis_queued(ctx, a, sc, ctx->sh_blind[axis], F + 3 + axis));
+  };
 
   // ---- GA: rows, checks, the slice and Y-range histograms ---------------------
-  const uint64_t n_mine = pre ? 0 : in->n;
-  const uint32_t nl = (uint32_t)n_mine;
-  const uint32_t shift = bin_shift(drop), yshift = bin_shift(nby);
-  static const bool one_on = [] {
-    const char *e = getenv("RK_SH_ONE");
-    return !(e && e[0] == '0');
-  }();
-  const bool one = one_on && P == 1;
-  const NwDigits ad = nw_plan(bit_length(vsize - 1));
-  const NwDigits yd = nw_plan(bit_length(2ull * nby - 1), 9);
-  const NwOrderPlan op1 = one ? nw_order_split_range(nl, 0, drop) : NwOrderPlan{};
-  uint32_t *hist = S.take<uint32_t>(SN_HIST, 3 * 4096);  // order / Y / member digit histograms
+  RecState R = rec_state(S, geo, in, p, one_on, false);
+  const uint32_t nl = R.nl, shift = R.shift, nby = R.nby;
   uint8_t *pay = S.msg_begin(P > 1 ? GA_END : GA_XH);
   uint32_t *wa = reinterpret_cast<uint32_t *>(pay + GA_WORDS);
   S.zero(F, 16 * 4);
-  Frags f{pre ? nullptr : in->x_start, pre ? nullptr : in->y_start,
-          pre ? nullptr : in->length, pre ? nullptr : in->strand, nl};
-  if (!pre && nl) {
-    if (one) {
-      S.zero(hist, 3 * 4096 * 4);
-      S.zero(S.ctrl + 32, 16 * 4);
-      nw_order_hist(*in, vsize, max_x, max_y, nby, op1.nseg ? op1.coarse : ad, yd, hist,
-                    hist + 4096, S.ctrl + 32, st);
-      k_sh_one_words<<<1, 64, 0, st>>>(S.ctrl + 32, wa);
-    } else {
-      ShRowsArgs ra{f, vsize, max_x, max_y, shift,
-                    P > 1 ? reinterpret_cast<uint32_t *>(pay + GA_XH) : nullptr, wa};
-      if (P > 1) {
-        ra.yhist = reinterpret_cast<uint32_t *>(pay + GA_YH);
-        ra.yshift = yshift;
-      }
-      kt_begin(st, KID_SH_ROWKEYS);
-      k_sh_rows<<<grid_for(nl, 256, P > 1 ? 1024 : 4096), 256, 0, st>>>(ra);
-      kt_end(st, KID_SH_ROWKEYS, 25.0 * nl);
-    }
-    S.launched("rows");
+  source_rows(S, R, wa, P > 1 ? reinterpret_cast<uint32_t *>(pay + GA_XH) : nullptr,
+              P > 1 ? reinterpret_cast<uint32_t *>(pay + GA_YH) : nullptr);
+  if (R.one && nl) {
+    k_sh_one_words<<<1, 64, 0, st>>>(S.ctrl + 32, wa);
+    S.launched("k_sh_one_words");
   }
   {
     uint64_t hostp[9];
-    hostp[0] = n_mine;
+    hostp[0] = in->n;
     for (int k = 0; k < 8; ++k) hostp[1 + k] = ctx->sh_fp[k];
-    if (S.msg_gather(pre, hostp, sizeof hostp)) throw pre ? pre : (int)RK_E_PEER;
+    if (S.msg_gather(0, hostp, sizeof hostp)) throw (int)RK_E_PEER;
   }
   uint64_t N = 0, row_base = 0;
   std::vector<uint64_t> nall(P), kept(P), fps((size_t)P * 8);
-  uint32_t anyerr = 0, nopack = 0, maxlen = 0;
+  uint32_t anyerr = 0, nopack = 0;
   std::vector<uint64_t> gh(NBINS, 0), gy(NBINS, 0);
   std::vector<uint32_t> hx_all(P > 1 ? (size_t)P * NBINS : 0);  // every rank's own row bins
   uint64_t fp = hmix(0x5eedull, P);
-  fp = hmix(hmix(hmix(fp, H), len_x), len_y);
+  fp = hmix(hmix(hmix(fp, R.H), p.len_x_hdr + 1), p.len_y_hdr + 1);
   for (uint32_t q = 0; q < P; ++q) {
     const uint8_t *mq = S.msg_of(q);
     std::memcpy(&nall[q], mq + GA_HOST, 8);
@@ -410,7 +391,7 @@ int classify_sharded_fast(Shard &S, const rk_frags_soa *in, const rk_params &p, 
     row_base += q < me ? nall[q] : 0;
     anyerr |= w[0];
     nopack |= w[20];
-    maxlen = w[21] > maxlen ? w[21] : maxlen;
+    R.maxlen = w[21] > R.maxlen ? w[21] : R.maxlen;
     kept[q] = w[25];
     fp = hmix(hmix(hmix(fp, nall[q]), kept[q]), w[21]);
     if (P > 1) {
@@ -422,7 +403,7 @@ int classify_sharded_fast(Shard &S, const rk_frags_soa *in, const rk_params &p, 
     }
   }
   *N_out = N;
-  *row_base_out = row_base;
+  *row_base_out = R.row_base = row_base;
   if (N >= 0xFFFFFFFFull) return RK_E_TOO_MANY;  // every rank sees the same N
   ss.n_in = nl;
   ss.n_total = N;
@@ -438,37 +419,19 @@ int classify_sharded_fast(Shard &S, const rk_frags_soa *in, const rk_params &p, 
   uint64_t new_fp[8] = {};
   uint64_t kept_all = 0;
   for (uint32_t q = 0; q < P; ++q) kept_all += kept[q];
-  const Bounds slice_keys = split_bounds(gh, shift, drop, P);
-  if (slice_max_rows(gh, slice_keys, shift, P, kept_all) >= (1ull << 30)) return RK_SHARD_FALLBACK;
+  R.kept = kept[me];
+  R.slice_keys = split_bounds(gh, shift, R.drop, P);
+  if (slice_max_rows(gh, R.slice_keys, shift, P, kept_all) >= (1ull << 30))
+    return RK_SHARD_FALLBACK;
   std::vector<uint64_t> mall(P, 0);  // every slice: the global histogram's bins between its bounds
   for (uint32_t q = 0; q < P; ++q)
-    mall[q] = P == 1 ? kept_all : bins_in(gh.data(), slice_keys, q, shift);
-  const uint32_t m = (uint32_t)mall[me];
-  uint64_t poff64 = 0;
-  for (uint32_t q = 0; q < me; ++q) poff64 += mall[q];
-  const uint32_t poff = (uint32_t)poff64;
-  Bounds slices{};
-  slices.P = P;
-  for (uint32_t q = 0, acc = 0; q <= MAXP; ++q) {
-    slices.b[q] = acc;
-    if (q < P) acc += (uint32_t)mall[q];
-  }
-  ss.n_slice = m;
-  const Bounds yb = split_bounds(gy, yshift, nby, P);
-  const uint64_t ylo = yb.b[me], yhi = yb.b[me + 1];
-  int64_t ylo_ext[MAXP] = {}, yhi_ext[MAXP] = {};
-  for (uint32_t q = 0; q < P; ++q) {
-    ylo_ext[q] = (int64_t)yb.b[q] - 1 - (int64_t)H;
-    yhi_ext[q] = (int64_t)yb.b[q + 1] + 1 + (int64_t)H;
-  }
+    mall[q] = P == 1 ? kept_all : bins_in(gh.data(), R.slice_keys, q, shift);
+  set_slices(S, R, mall);
+  const uint32_t m = R.m, poff = R.poff;
+  R.yb = split_bounds(gy, R.yshift, nby, P);
+  const Bounds &slices = R.slices, &yb = R.yb;
   uint64_t thr[MAXP];
-  for (uint32_t g = 0; g < MAXP; ++g) {
-    thr[g] = ~0ull;
-    if (g < P && mall[g]) {
-      const uint64_t bmin = slice_keys.b[g] / 10;  // xStart >= 10*key, centre >= xStart
-      thr[g] = bmin >= 1 + H ? bmin - 1 - H : 0;
-    }
-  }
+  lead_in_thresholds(thr, R.mall, R.slice_keys, R.H);
   uint64_t fbk[MAXP], lbk[MAXP];  // every Y range's first and last bucket
   for (uint32_t q = 0; q < MAXP; ++q) {
     const bool ne = q < P && yb.b[q] < yb.b[q + 1];
@@ -482,13 +445,12 @@ int classify_sharded_fast(Shard &S, const rk_frags_soa *in, const rk_params &p, 
     pay = S.msg_begin((size_t)(2 * P * P + 2 * P) * 4);
     if (nl) {
       ShCountArgs ca{};
-      ca.f = f;
-      ca.drop = drop;
+      ca.f = R.f;
+      ca.drop = R.drop;
       ca.P = P;
-      ca.sk = slice_keys;
+      ca.sk = R.slice_keys;
+      y_halo_ranges(yb, P, R.H, ca.ylo, ca.yhi);
       for (uint32_t q = 0; q < MAXP; ++q) {
-        ca.ylo[q] = ylo_ext[q];
-        ca.yhi[q] = yhi_ext[q];
         ca.thr[q] = thr[q];
         ca.fb[q] = fbk[q];
         ca.lb[q] = lbk[q];
@@ -543,137 +505,41 @@ int classify_sharded_fast(Shard &S, const rk_frags_soa *in, const rk_params &p, 
 
   // ---- 2: rows -> slice owners as 16-B records ----------------------------------
   tphase = std::chrono::steady_clock::now();
-  RowOp16 rop{f, slice_keys, drop, (uint32_t)row_base, nullptr};
-  PartPlan pp;
-  rop.out = S.take<uint4>(SN_SROWS, (size_t)nl + 1);
-  const bool fast = one && kept[0] == nl;  // the order sort reads the rows themselves
-  if (fast) {
-    S.identity_plan(nl, pp);
-  } else if (P == 1 && kept[0] == nl) {
-    S.emit_identity(rop, nl, pp);
-  } else {
-    uint64_t cnt[MAXP] = {};
-    for (uint32_t q = 0; q < P; ++q)
-      cnt[q] = P == 1 ? kept[0] : bins_in(&hx_all[(size_t)me * NBINS], slice_keys, q, shift);
-    S.plan_counts(rop, nl, pp, cnt);
-    S.emit(rop, pp);
-  }
   uint64_t rfrom[MAXP] = {};
   for (uint32_t q = 0; q < P; ++q)
-    rfrom[q] = P == 1 ? pp.total : bins_in(&hx_all[(size_t)q * NBINS], slice_keys, me, shift);
+    rfrom[q] = P == 1 ? R.kept : bins_in(&hx_all[(size_t)q * NBINS], R.slice_keys, me, shift);
   uint32_t mrecv = 0;
-  const uint4 *rin = xchg<uint4>(S, knownA, rop.out, pp, rfrom, SN_RIN, &mrecv);
+  const uint4 *rin = rows_to_owners(S, R, P > 1 ? &hx_all[(size_t)me * NBINS] : nullptr,
+                                    FastExchange{S, knownA, rfrom}, &mrecv);
   if (mrecv != m) {
     ctx->err = "fast path: slice size differs from the histogram's";
     throw RK_E_INTERNAL;
   }
 
   // ---- 3: the slice's processing order, its Y records ---------------------------
-  uint32_t *ahist = hist, *yhist = hist + 4096, *ehist = hist + 2 * 4096;
-  if (!fast) S.zero(ahist, 3 * 4096 * 4);
-  const size_t sw = nw_status_words(m + 1);
-  uint32_t *astat = S.take<uint32_t>(SN_STAT, sw);
-  uint4 *Ra = S.take<uint4>(SN_RA, m + 1), *Rb = S.take<uint4>(SN_RB, m + 1);
-  uint4 *yown = S.take<uint4>(SN_YOWN, (size_t)m * 3 / 4 + 2);
-  const NwOrderPlan op = fast ? op1 : nw_order_split_range(m, slice_keys.b[me], slice_keys.b[me + 1]);
-  ss.order_split = op.nseg ? 1u : 0u;
-  const uint64_t span = (slice_keys.b[me + 1] - slice_keys.b[me]) / 10 + 2;
-  NwChunkCounts own_cc{};
-  own_cc.W = nw_chunk_width(m, (uint32_t)(span < nbx ? span : nbx));
-  while ((1u << own_cc.lgW) < own_cc.W) ++own_cc.lgW;
-  own_cc.nch = nw_chunks(nbx, own_cc.W);
-  bool own_counts = false;
-  if (m && op.nseg) {
-    uint32_t *chist = S.take<uint32_t>(SN_CHIST, nw_seg_words(m));
-    uint32_t *coff = S.take<uint32_t>(SN_COFF, nw_seg_words(m));
-    own_cc.cnts = S.take<uint32_t>(SN_XCNT0, (size_t)3 * own_cc.nch + 2);
-    if (fast) {
-      nw_order_sort_split_coarse(*in, op, ahist, astat, Ra, Rb, chist,
-                                 ZeroRegion{own_cc.cnts, ((size_t)3 * own_cc.nch + 1) * 4}, vsize,
-                                 st, nullptr);
-      nw_order_sort_split_fine(nl, m, nby, op, Ra, Rb, yown, rop.out, chist, coff,
-                               S.scan_scratch(SL_PSCAN, (size_t)op.nseg + 1), &own_cc, st);
-    } else {
-      nw_rec_hist(rin, 16, m, op.kbase, op.coarse, ahist, st);
-      nw_order_sort_recs_split(rin, m, nby, poff, op, ahist, astat, Ra, Rb, yown,
-                               const_cast<uint4 *>(rin), chist, coff,
-                               S.scan_scratch(SL_PSCAN, (size_t)op.nseg + 1), &own_cc, st);
-    }
-    own_counts = true;
-    S.launched("order sort");
-  } else if (m) {
-    if (fast) {
-      nw_order_sort(*in, vsize, nby, ad, ahist, astat, Ra, Rb, yown, st);
-    } else {
-      nw_rec_hist(rin, 16, m, 0, ad, ahist, st);
-      nw_order_sort_recs(rin, m, nby, poff, ad, ahist, astat, Ra, Rb, yown, st);
-    }
-    S.launched("order sort");
-  }
+  slice_order(S, R, rin);
 
   // ---- 4: Y records -> Y-range owners (+ halos) ----------------------------------
-  YOp12 yop{};
-  yop.yrec = reinterpret_cast<const uint3 *>(yown);
-  yop.nby = nby;
-  yop.P = P;
-  yop.shift = yshift;
-  for (uint32_t q = 0; q < MAXP; ++q) {
-    yop.lo[q] = q < P ? ylo_ext[q] : 0;
-    yop.hi[q] = q < P ? yhi_ext[q] : 0;
-  }
+  YOp12 yop = y_op(R, P);
   PartPlan ypp;
-  if (P == 1) {
-    S.identity_plan(m, ypp);
-  } else {
-    uint64_t cnt[MAXP] = {};
-    for (uint32_t q = 0; q < P; ++q) cnt[q] = Yat(me, q);
-    ypp.mcache = S.take<uint32_t>(SL_YMASK, m + 1);  // the X-hit bytes follow the same masks
-    S.plan_counts(yop, m, ypp, cnt);
-  }
-  const bool y_self = ypp.total == m && ypp.cnt[me] == m;
-  if (!y_self) {
-    yop.out = S.take<uint3>(SN_SY, ypp.total + 1);
-    S.emit(yop, ypp);
-  }
-  uint64_t yfrom[MAXP] = {};
-  for (uint32_t q = 0; q < P; ++q) yfrom[q] = P == 1 ? m : Yat(q, me);
-  uint32_t ny = 0;
-  const uint3 *yr = xchg<uint3>(S, knownA, y_self ? yop.yrec : yop.out, ypp, yfrom, SN_YR, &ny);
+  uint64_t ysend[MAXP] = {}, yfrom[MAXP] = {};
+  for (uint32_t q = 0; q < P; ++q) ysend[q] = Yat(me, q), yfrom[q] = P == 1 ? m : Yat(q, me);
+  y_to_owners(S, R, yop, ypp, ysend, FastExchange{S, knownA, yfrom});
+  const uint32_t ny = R.ny;
   if (ny != ny64) {
     ctx->err = "fast path: Y range size differs from the counts";
     throw RK_E_INTERNAL;
   }
-  ss.y_entries = ny;
-  uint8_t *ycode = S.take<uint8_t>(SL_YCODE, ny + 1);
-  uint8_t *ystate = S.take<uint8_t>(SL_YSTATE, ny + 1);
-  uint32_t *ywin = S.take<uint32_t>(SL_YWIN, ny + 1);
-  uint8_t *yused = S.take<uint8_t>(SL_YUSED, ny + 1);
-  uint32_t *par_l = S.take<uint32_t>(SN_PARL, ny + 1);
-  uint32_t *ystat = S.take<uint32_t>(SN_YSTAT, nw_status_words(ny + 1));
-  uint4 *yA = S.take<uint4>(SN_YA, (size_t)ny * 3 / 4 + 2), *yB = S.take<uint4>(SN_YB, (size_t)ny * 3 / 4 + 2);
-  Csr cy{};
-  cy.key = S.take<uint32_t>(SN_YKEY, ny + 1);
-  cy.ent = S.take<uint32_t>(SN_YENT, ny + 1);
-  cy.pk = S.take<uint2>(SN_YPK, ny + 1);
-  cy.nbd = S.take<uint8_t>(SN_YNBD, ny + 1);
-  cy.state = S.take<uint8_t>(SN_YST, ny + 1);
-  uint32_t *ybits = S.take<uint32_t>(SN_XBITS, ny / 32 + 2);
-  S.hip(hipEventRecord(ctx->fork, st), "fork");
-  S.hip(hipStreamWaitEvent(st2, ctx->fork, 0), "fork wait");
-  if (ny) {
-    if (!solo) {  // (one rank: no halo classes, no verification, no parents to send)
-      k_sh_ycode<<<grid_for(ny, 256), 256, 0, st2>>>(yr, ny, nby, ylo, yhi, ycode);
-      S.launched("k_sh_ycode");
-    }
-    if (!fast) nw_rec_hist(yr, 12, ny, 0, yd, yhist, st2);
-  }
-  S.hip(hipEventRecord(ctx->join, st2), "join");
+  y_buffers(S, R);
+  const uint64_t ylo = R.ylo, yhi = R.yhi;
+  // (one rank: no halo classes, no verification, no parents to send)
+  y_beside_x(S, R, !solo);
   ss.ms_y = ms_since(tphase);
 
   // ---- 5: X lead-in halo from earlier slices -------------------------------------
   tphase = std::chrono::steady_clock::now();
   GhostOp16 gop{};
-  gop.R = Ra;
+  gop.R = R.Ra;
   gop.P = P;
   gop.me = me;
   gop.poff = poff;
@@ -688,14 +554,9 @@ int classify_sharded_fast(Shard &S, const rk_frags_soa *in, const rk_params &p, 
   }
   PartPlan hpp;
   if (hsend_tot && m) {
-    // the suffix of the slice whose centres can reach a later slice's lead-in
-    // starts on the device (no readback): entries before it select nothing
-    uint64_t thr_min = ~0ull;
-    for (uint32_t g = me + 1; g < P; ++g) thr_min = thr[g] < thr_min ? thr[g] : thr_min;
-    const uint64_t reach = thr_min * 100, half = maxlen / 2;
-    const uint64_t key0 = reach > half + 10 ? (reach - half) / 10 - 1 : 0;
-    k_lower_bound16<<<1, 1, 0, st>>>(Ra, m, key0, S.ctrl + 22);
-    S.launched("k_lower_bound16");
+    // the suffix starts on the device (no readback): entries before it select
+    // nothing
+    lead_in_suffix(S, R, thr);
     gop.dbase = S.ctrl + 22;
     S.plan_counts(gop, m, hpp, hsend);
   } else {
@@ -703,8 +564,9 @@ int classify_sharded_fast(Shard &S, const rk_frags_soa *in, const rk_params &p, 
   }
   gop.out = S.take<uint4>(SN_SHALO, hpp.total + 1);
   if (hpp.n) S.emit(gop, hpp);
+  const FastExchange ex_halo{S, knownA, hfrom};
   uint32_t G = 0;
-  const uint4 *hx = xchg<uint4>(S, knownA, gop.out, hpp, hfrom, SN_HX, &G);
+  const uint4 *hx = ex_halo(gop.out, hpp, SN_HX, &G);
   if (G != G64) {
     ctx->err = "fast path: lead-in size differs from the counts";
     throw RK_E_INTERNAL;
@@ -712,57 +574,24 @@ int classify_sharded_fast(Shard &S, const rk_frags_soa *in, const rk_params &p, 
   ss.x_ghosts = G;
 
   // ---- 6: X axis over [halo ; own], its sweeps queued -----------------------------
-  uint32_t *xg = S.take<uint32_t>(SL_XG, m + 1);
-  uint8_t *xused = S.take<uint8_t>(SN_XGUSED, G + 1);
-  S.zero(S.ctrl + 6, 4);
-  const uint32_t mx = G + m;
-  if (mx) {
-    NwChunkCounts cc{};
-    cc.W = nw_chunk_width(mx, (uint32_t)(span < nbx ? span : nbx));
-    while ((1u << cc.lgW) < cc.W) ++cc.lgW;
-    cc.nch = nw_chunks(nbx, cc.W);
-    cc.cnts = S.take<uint32_t>(SN_XCNT, (size_t)3 * cc.nch + 2);
-    uint32_t *xoff = S.take<uint32_t>(SN_XOFF, (size_t)3 * cc.nch + 2);
-    if (own_counts && cc.W == own_cc.W) {
-      S.hip(hipMemcpyAsync(cc.cnts, own_cc.cnts, ((size_t)3 * cc.nch + 1) * 4,
-                           hipMemcpyDeviceToDevice, st), "counts copy");
-      nw_x_count_add(hx, G, cc, st);
-    } else {
-      nw_x_count(Ra, mx, cc, st, hx, G);
-    }
-    exclusive_scan_u32(cc.cnts, xoff, (size_t)3 * cc.nch + 1,
-                       S.scan_scratch(SL_PSCAN, (size_t)3 * cc.nch + 1), st);
-    Csr cx{};
-    cx.key = S.take<uint32_t>(SN_XKEY, mx + 1);
-    cx.ent = S.take<uint32_t>(SN_XENT, mx + 1);
-    cx.pk = S.take<uint2>(SN_XPK, mx + 1);
-    cx.nbd = S.take<uint8_t>(SN_XNBD, mx + 1);
-    cx.state = S.take<uint8_t>(SN_XSTATE, mx + 1);
-    uint32_t *xpos = S.take<uint32_t>(SN_XPOS, mx + 1);
-    uint4 *erec = S.take<uint4>(SN_EREC, (size_t)mx * 3 / 4 + 2);
-    // one rank: entry ids are processing indices, and both axes write their
-    // decisions straight into the parent words (as on one device)
-    uint32_t *par = solo ? xg : S.take<uint32_t>(SN_PAR, mx + 1);
-    nw_x_chunks(Ra, mx, nbx, max_x, maxlen, xoff, cx, xpos, erec, S.ctrl, cc.W, st, hx, G);
-    S.launched("X chunks");
-    Axis ax{cx.key, cx.ent, nullptr, nullptr, cx.state, nullptr, par, cx.pk, cx.nbd,
-            S.take<uint32_t>(SL_RLEN, mx), S.take<uint32_t>(SL_RBEG, mx), mx, max_x,
-            p.len_ratio, p.pos_ratio};
-    SweepScratch sc{S.take<uint32_t>(SL_RUNS, runs_scratch_words(mx)),
-                    S.take<uint8_t>(SL_WPEND, mx / 64 + 1), S.take<uint8_t>(SL_RPEND, mx),
-                    S.ctrl + 64, S.ctrl + 4};
-    S.check(resolve_axis_queued(ctx, ax, sc, ctx->sh_blind[0], F + 3));
-    if (solo) {  // the X hits as the Y sort's bitmask (k_nw_x_bits, as on one device)
-      nw_x_bits(xpos, cx.state, m, ybits, st);
-      S.launched("k_nw_x_bits");
-    } else {
-      kt_begin(st, KID_SH_XOWN);
-      k_sh_x_own_fast<<<grid_for(mx, 256, 4096), 256, 0, st>>>(xpos, cx.state, par, hx, G, m,
-                                                               poff, xg, xused, slices, me, gc_lk);
-      kt_end(st, KID_SH_XOWN, 0.0);
-      S.launched("k_sh_x_own_fast");
-    }
-  }
+  x_buffers(S, R, G);
+  uint32_t *xg = R.xg;
+  // one rank: entry ids are processing indices, and both axes write their
+  // decisions straight into the parent words (as on one device); the X hits
+  // become the Y sort's bitmask (k_nw_x_bits)
+  solve_x(S, R, hx, G, solo ? xg : nullptr, resolve,
+          [&](const uint32_t *xpos, const uint8_t *state, const uint32_t *par, uint32_t mx) {
+            if (solo) {
+              nw_x_bits(xpos, state, m, R.ybits, st);
+              S.launched("k_nw_x_bits");
+            } else {
+              kt_begin(st, KID_SH_XOWN);
+              k_sh_x_own_fast<<<grid_for(mx, 256, 4096), 256, 0, st>>>(
+                  xpos, state, par, hx, G, m, poff, xg, R.xused, slices, me, gc_lk);
+              kt_end(st, KID_SH_XOWN, 0.0);
+              S.launched("k_sh_x_own_fast");
+            }
+          });
   // the owners' final states of the lead-in (the same selection as the records)
   if (P > 1) {
     GhostOp16 sop = gop;
@@ -774,11 +603,10 @@ int classify_sharded_fast(Shard &S, const rk_frags_soa *in, const rk_params &p, 
     sop.sout = S.take<uint8_t>(SL_SEND, spp.total + 1);
     if (spp.n) S.emit(sop, spp);
     uint32_t G2 = 0;
-    const uint8_t *xown = xchg<uint8_t>(S, knownA, sop.sout, spp, hfrom, SL_XOWN, &G2);
-    const uint64_t bmin_me = slice_keys.b[me] / 10;
-    const uint64_t rel_x = bmin_me >= 1 ? bmin_me - 1 : 0;  // relevant: probed by own queries
+    const uint8_t *xown = ex_halo(sop.sout, spp, SL_XOWN, &G2);
     if (G) {
-      k_cmp_x16<<<grid_for(G, 256, 1024), 256, 0, st>>>(hx, G, rel_x, xused, xown, F + 1);
+      k_cmp_x16<<<grid_for(G, 256, 1024), 256, 0, st>>>(hx, G, relevant_from(R, me), R.xused, xown,
+                                                        F + 1);
       S.launched("k_cmp_x16");
     }
     ss.x_rounds = 1;
@@ -787,79 +615,48 @@ int classify_sharded_fast(Shard &S, const rk_frags_soa *in, const rk_params &p, 
 
   // ---- 7: X-hit bytes after the Y records, the Y sort, its sweeps ----------------
   tphase = std::chrono::steady_clock::now();
-  if (solo) {
-    S.hip(hipStreamWaitEvent(st, ctx->join, 0), "join wait");
-  } else {
-    YOp12 xop = yop;
-    xop.xg = xg;
-    PartPlan xpp;
-    xop.xout = S.take<uint8_t>(SN_SXH, (size_t)ypp.total + 1);
-    if (P == 1) {
-      S.emit_identity(xop, m, xpp);
-    } else {
-      xpp.mcache = ypp.mcache;
-      xpp.mread = true;
-      S.plan_same(xop, m, xpp, ypp);
-      S.emit(xop, xpp);
-    }
-    uint32_t n2 = 0;
-    const uint8_t *xh = xchg<uint8_t>(S, knownA, xop.xout, xpp, yfrom, SL_YXH, &n2);
-    S.hip(hipStreamWaitEvent(st, ctx->join, 0), "join wait");
-    if (ny) {
-      kt_begin(st, KID_SH_MERGE);
-      k_sh_xhit_bits<<<grid_for(ny, 256), 256, 0, st>>>(xh, ny, ycode, ybits);
-      kt_end(st, KID_SH_MERGE, 0.0);
-      S.launched("k_sh_xhit_bits");
-    }
-  }
+  if (solo) S.hip(hipStreamWaitEvent(st, ctx->join, 0), "join wait");
+  else xhits_follow_y(S, R, yop, ypp, FastExchange{S, knownA, yfrom});
   if (ny) {
-    nw_y_sort_after_x(yB, yA, ny, yd, yhist, ystat, cy, nby, max_y, ybits, st,
-                      reinterpret_cast<const uint4 *>(yr));
+    nw_y_sort_after_x(R.yB, R.yA, ny, R.yd, R.yhist, R.ystat, R.cy, nby, R.max_y, R.ybits, st,
+                      reinterpret_cast<const uint4 *>(R.yr));
     S.launched("Y sort");
-    Axis ay{cy.key, cy.ent, nullptr, nullptr, cy.state, nullptr, solo ? xg : par_l, cy.pk, cy.nbd,
-            S.take<uint32_t>(SL_RLEN, ny), S.take<uint32_t>(SL_RBEG, ny), ny, max_y, p.len_ratio,
-            p.pos_ratio};
-    ay.par_dev = true;
-    SweepScratch sc{S.take<uint32_t>(SL_RUNS, runs_scratch_words(ny)),
-                    S.take<uint8_t>(SL_WPEND, ny / 64 + 1), S.take<uint8_t>(SL_RPEND, ny),
-                    S.ctrl + 64, S.ctrl + 4};
-    S.check(resolve_axis_queued(ctx, ay, sc, ctx->sh_blind[1], F + 4));
   }
+  sweep_y(S, R, ny, solo ? xg : R.par_l, resolve);
   if (ny && !solo) {
     kt_begin(st, KID_SH_YRES);
     // (a grid of at most 2048 blocks: each block adds its counts with global
     // atomics on a few shared words, and 65536 blocks serialised them there)
-    k_sh_y_results_fast<<<grid_for(ny, 256, 2048), 256, 0, st>>>(yr, ycode, ny, par_l, ystate, ywin,
-                                                           poff, m, xg, slices, me, gc_pc, gc_rc,
-                                                           gc_lk, F);
+    k_sh_y_results_fast<<<grid_for(ny, 256, 2048), 256, 0, st>>>(
+        R.yr, R.ycode, ny, R.par_l, R.ystate, R.ywin, poff, m, xg, slices, me, gc_pc, gc_rc, gc_lk,
+        F);
     kt_end(st, KID_SH_YRES, 0.0);
     S.launched("k_sh_y_results_fast");
   }
   // the owners' states of the relevant Y halo entries
   if (P > 1) {
-    const RelOp relop0{ycode, ylo ? owner_of_host(yb, ylo - 1) : 0u,
-                       yhi < nby ? owner_of_host(yb, yhi) : 0u, nullptr};
-    RelOp relop = relop0;
-    uint64_t ysend[MAXP] = {}, yrecv[MAXP] = {};
+    RelOp relop{R.ycode, ylo ? owner_of_host(yb, ylo - 1) : 0u,
+                yhi < nby ? owner_of_host(yb, yhi) : 0u, nullptr};
+    uint64_t ysts[MAXP] = {}, ystr[MAXP] = {};
     for (uint32_t q = 0; q < P; ++q) {
-      ysend[q] = Ys[(size_t)me * P + q];
-      yrecv[q] = Ys[(size_t)q * P + me];
+      ysts[q] = Ys[(size_t)me * P + q];
+      ystr[q] = Ys[(size_t)q * P + me];
     }
     const bool lonely = ylo == 0 && yhi == yb.b[P];
     PartPlan rp;
     if (lonely) S.zero_plan(ny, rp);
-    else S.plan_counts(relop, ny, rp, yrecv);
+    else S.plan_counts(relop, ny, rp, ystr);
     const uint32_t nrel = (uint32_t)rp.total;
     uint32_t *relidx = S.take<uint32_t>(SL_RELIDX, nrel + 1);
     relop.out = relidx;
     if (!lonely) S.emit(relop, rp);
     if (nrel) {
-      k_set_used<<<grid_for(nrel, 256), 256, 0, st>>>(relidx, nrel, nullptr, ystate, yused);
+      k_set_used<<<grid_for(nrel, 256), 256, 0, st>>>(relidx, nrel, nullptr, R.ystate, R.yused);
       S.launched("k_set_used");
     }
     YStateOp yso{};
-    yso.code = ycode;
-    yso.ystate = ystate;
+    yso.code = R.ycode;
+    yso.ystate = R.ystate;
     for (uint32_t q = 0; q < P; ++q) {
       if (q == me) continue;
       if (yb.b[q + 1] == ylo) yso.first_mask |= 1u << q;
@@ -868,17 +665,17 @@ int classify_sharded_fast(Shard &S, const rk_frags_soa *in, const rk_params &p, 
     const bool none = !yso.first_mask && !yso.last_mask;
     PartPlan sp;
     if (none) S.zero_plan(ny, sp);
-    else S.plan_counts(yso, ny, sp, ysend);
+    else S.plan_counts(yso, ny, sp, ysts);
     yso.out = S.take<uint8_t>(SL_SEND, sp.total + 1);
     if (!none) S.emit(yso, sp);
     uint32_t n2 = 0;
-    const uint8_t *rys = xchg<uint8_t>(S, knownA, yso.out, sp, yrecv, SL_RYS, &n2);
+    const uint8_t *rys = xchg<uint8_t>(S, knownA, yso.out, sp, ystr, SL_RYS, &n2);
     if (n2 != nrel) {
       ctx->err = "fast path: Y halo state count mismatch";
       throw RK_E_INTERNAL;
     }
     if (nrel) {
-      k_cmp_y<<<grid_for(nrel, 256, 1024), 256, 0, st>>>(relidx, nrel, yused, rys, F + 2);
+      k_cmp_y<<<grid_for(nrel, 256, 1024), 256, 0, st>>>(relidx, nrel, R.yused, rys, F + 2);
       S.launched("k_cmp_y");
     }
     ss.y_rounds = 1;
@@ -887,40 +684,24 @@ int classify_sharded_fast(Shard &S, const rk_frags_soa *in, const rk_params &p, 
 
   // ---- 8: roots -------------------------------------------------------------------
   tphase = std::chrono::steady_clock::now();
-  uint32_t *lpar = S.take<uint32_t>(SL_LPAR, m + 1);
-  uint32_t *ext = S.take<uint32_t>(SL_EXT, m + 1);
-  uint32_t *isroot = S.take<uint32_t>(SL_ISROOT, m + 2);
-  uint32_t *lrank = S.take<uint32_t>(SL_LRANK, m + 2);
-  uint32_t *junk = S.take<uint32_t>(SL_JUNK, m + 1);
-  uint32_t *lab = S.take<uint32_t>(SL_LAB, m + 1);
-  uint32_t *cur = S.take<uint32_t>(SL_CUR, m + 1);
+  const RootBufs rb = root_buffers(S, m);
+  uint32_t *lpar = rb.lpar, *lrank = rb.lrank, *lab = rb.lab, *cur = rb.cur;
   // local parents (X winners; the X misses' Y winners of this rank's slice
   // are in place, the other ranks' arrive with the parent exchange), chains
   // compressed inside the slice by a jumping pass and a pass over the chains
   // it left open (no readback between them; a chain still open after both is
   // a crafted input: its flag, checked with the next gather, repeats the call
   // the careful way)
-  auto local_roots = [&](const ParRec *prr, uint32_t npar) {
-    if (!m) return;
-    if (npar) {
-      kt_begin(st, KID_SHARD_AUX);
-      k_par_scatter<<<grid_for(npar, 256), 256, 0, st>>>(prr, npar, poff, m, xg, S.ctrl);
-      kt_end(st, KID_SHARD_AUX, 0.0);
-    }
-    kt_begin(st, KID_SHARD_AUX);
-    k_local_par<<<grid_for(m, 256), 256, 0, st>>>(xg, m, poff, lpar, ext, isroot, S.ctrl);
-    kt_end(st, KID_SHARD_AUX, 0.0);
-    S.launched("parents");
-    Proc jp{};
-    jp.par = lpar;
-    S.zero(S.ctrl + 3, 4);
-    jump_listed(jp, m, junk, S.ctrl, S.take<uint32_t>(SL_JLIST, m + 1), S.ctrl + 10, S.ctrl + 3,
-                st);
-    S.launched("jump_listed");
-    exclusive_scan_u32(isroot, lrank, (size_t)m + 1, S.scan_scratch(SL_SCAN, m + 1), st);
+  const auto roots = [&](const ParRec *prr, uint32_t npar) {
+    local_roots(S, rb, xg, prr, npar, m, poff, [&](Proc jp, uint32_t *isnew) {
+      S.zero(S.ctrl + 3, 4);
+      jump_listed(jp, m, isnew, S.ctrl, S.take<uint32_t>(SL_JLIST, m + 1), S.ctrl + 10,
+                  S.ctrl + 3, st);
+      S.launched("jump_listed");
+    });
   };
   if (P == 1) {
-    local_roots(nullptr, 0);
+    roots(nullptr, 0);
     if (m) {  // the slice's roots: its new groups
       k_copy_word<<<1, 64, 0, st>>>(lrank + m, gc_rc);
       S.launched("k_copy_word");
@@ -930,7 +711,7 @@ int classify_sharded_fast(Shard &S, const rk_frags_soa *in, const rk_params &p, 
   S.launched("k_msg_head");
   if (S.msg_gather(S.sticky)) throw S.sticky ? S.sticky : (int)RK_E_PEER;
   uint32_t anyerr2 = 0, retry = 0, wide = 0;
-  std::vector<uint64_t> Pm((size_t)P * P, 0), R(P, 0), Lm((size_t)P * P, 0);
+  std::vector<uint64_t> Pm((size_t)P * P, 0), Rt(P, 0), Lm((size_t)P * P, 0);
   for (uint32_t q = 0; q < P; ++q) {
     const uint32_t *w = reinterpret_cast<const uint32_t *>(S.msg_of(q));
     anyerr2 |= w[0];
@@ -939,7 +720,7 @@ int classify_sharded_fast(Shard &S, const rk_frags_soa *in, const rk_params &p, 
     const uint32_t *pc = w + GW_END / 4, *rc = pc + P, *lk = rc + P;
     for (uint32_t s = 0; s < P; ++s) {
       Pm[(size_t)q * P + s] = pc[s];
-      R[s] += rc[s];
+      Rt[s] += rc[s];
     }
     for (size_t j = 0; j < (size_t)P * P; ++j) Lm[j] += lk[j];
     fp = hbytes(fp, w, GW_END + (size_t)(2 * P + P * P) * 4);
@@ -948,7 +729,7 @@ int classify_sharded_fast(Shard &S, const rk_frags_soa *in, const rk_params &p, 
   S.check(err_status(ctx, anyerr2 & ~(uint32_t)ERRB_WIDE_LENGTH));
   const bool narrow = wide == 0;  // every in-group sort key fits 32 bits
   uint64_t Gtot = 0, goff = 0;
-  for (uint32_t q = 0; q < P; ++q) Gtot += R[q], goff += q < me ? R[q] : 0;
+  for (uint32_t q = 0; q < P; ++q) Gtot += Rt[q], goff += q < me ? Rt[q] : 0;
   bool links = false;
   for (uint64_t v : Lm) links |= v != 0;
   new_fp[1] = fp;
@@ -956,21 +737,16 @@ int classify_sharded_fast(Shard &S, const rk_frags_soa *in, const rk_params &p, 
   S.alloc_locked = knownB;
   ss.fast_stages |= knownB ? 2u : 0u;
 
-  uint32_t *gid_own = junk;
-  const uint32_t gshift = bin_shift(Gtot);
-  MemOpNw mop{};
-  // the member records: the X chunk kernel wrote them behind the halo's
-  const uint2 *erk = reinterpret_cast<const uint2 *>(S.take<uint4>(SN_EREC, (size_t)mx * 3 / 4 + 2));
-  mop.gid = gid_own;
-  mop.erk = erk + G;
-  mop.ehi = reinterpret_cast<const uint32_t *>(erk + mx) + G;
-  mop.shift = gshift;
+  uint32_t *gid_own = rb.junk;
+  const uint2 *erk = nullptr;
+  MemOpNw mop = member_op(S, R, gid_own, Gtot, &erk);
+  const uint32_t gshift = mop.shift;
   mop.narrow = narrow;
   bool knownC = knownB;
   std::vector<uint32_t> ghist_all;  // every rank's gid histogram (the last GD)
   if (P > 1) {
     // the parent exchange: the sizes every Y owner counted
-    ParOp12 pop{yr, ycode, slices, ywin, me, nullptr};
+    ParOp12 pop{R.yr, R.ycode, slices, R.ywin, me, nullptr};
     uint64_t psend[MAXP] = {}, pfrom[MAXP] = {};
     for (uint32_t q = 0; q < P; ++q) {
       psend[q] = Pm[(size_t)me * P + q];
@@ -982,9 +758,9 @@ int classify_sharded_fast(Shard &S, const rk_frags_soa *in, const rk_params &p, 
     S.emit(pop, ppp);
     uint32_t npar = 0;
     const ParRec *prr = xchg<ParRec>(S, knownB, pop.out, ppp, pfrom, SL_PR, &npar);
-    local_roots(prr, npar);
+    roots(prr, npar);
     if (m) {
-      k_expect1<<<1, 64, 0, st>>>(lrank + m, (uint32_t)R[me], F, RETRY_EXPECT);
+      k_expect1<<<1, 64, 0, st>>>(lrank + m, (uint32_t)Rt[me], F, RETRY_EXPECT);
       S.launched("k_expect1");
     }
     // cross-slice links: request rounds, the first sized by the links the Y
@@ -996,11 +772,12 @@ int classify_sharded_fast(Shard &S, const rk_frags_soa *in, const rk_params &p, 
     }
     if (links && m) {
       kt_begin(st, KID_SHARD_AUX);
-      k_init_labels<<<grid_for(m, 256), 256, 0, st>>>(lpar, ext, lrank, (uint32_t)goff, m, lab,
+      k_init_labels<<<grid_for(m, 256), 256, 0, st>>>(lpar, rb.ext, lrank, (uint32_t)goff, m, lab,
                                                       cur);
       kt_end(st, KID_SHARD_AUX, 0.0);
       S.launched("k_init_labels");
     }
+    const ReqOp rq{lpar, lab, cur, slices, nullptr, nullptr};
     PartPlan rpp;
     bool planned = false;  // rpp already planned on the device (a later round)
     for (uint32_t round = 0;; ++round) {
@@ -1010,47 +787,22 @@ int classify_sharded_fast(Shard &S, const rk_frags_soa *in, const rk_params &p, 
       }
       if (links) {
         ++ss.root_rounds;
-        ReqOp rq{lpar, lab, cur, slices, nullptr, nullptr};
         if (!planned) S.plan_counts(rq, m, rpp, rq_send);
-        rq.req = S.take<uint32_t>(SL_REQ, rpp.total + 1);
-        rq.src = S.take<uint32_t>(SL_SRC, rpp.total + 1);
-        S.emit(rq, rpp);
-        uint32_t nq = 0;
-        const uint32_t *rqs = xchg<uint32_t>(S, knownC, rq.req, rpp, rq_recv, SL_RQ, &nq);
-        uint2 *resp = nullptr, *back = nullptr;
-        int rrc = RK_OK;
-        try {
-          resp = S.take<uint2>(SL_RESP, nq + 1);
-          back = S.take<uint2>(SL_BACK, rpp.total + 1);
-          if (fault_here(ctx, "k_respond")) throw (int)RK_E_NOMEM;
-          if (nq) {
-            k_respond<<<grid_for(nq, 256), 256, 0, st>>>(rqs, nq, poff, m, lpar, lab, cur, resp,
-                                                          S.ctrl);
-            S.launched("k_respond");
-          }
-        } catch (int code) {
-          rrc = code;
-        }
-        if (!knownC) {
-          S.agree(rrc);  // the response buffers were sized by skewed counts
-        } else if (rrc) {
-          S.sticky = rrc;  // (no agreement point here: reported by the next gather)
-          ctx->err = "a local failure before the response exchange";
-        }
-        uint64_t sb[MAXP], rb[MAXP];
-        for (uint32_t q = 0; q < P; ++q) sb[q] = rq_recv[q] * sizeof(uint2), rb[q] = rpp.cnt[q] * sizeof(uint2);
-        S.run_a2a(resp, sb, back, rb);
-        if (rpp.total) {
-          k_apply<<<grid_for((uint32_t)rpp.total, 256), 256, 0, st>>>(back, rq.src,
-                                                                      (uint32_t)rpp.total, lab, cur);
-          S.launched("k_apply");
-        }
+        request_round(S, rb, slices, m, poff, rpp, FastExchange{S, knownC, rq_recv}, rq_recv,
+                      [&](int rrc) {
+                        if (!knownC) {
+                          S.agree(rrc);  // the response buffers were sized by skewed counts
+                        } else if (rrc) {
+                          S.sticky = rrc;  // (no agreement point here: reported by the next gather)
+                          ctx->err = "a local failure before the response exchange";
+                        }
+                      },
+                      false);
       }
       // GD: the next round's request counts, the jumping flag, the gid histogram
       uint32_t *gd = reinterpret_cast<uint32_t *>(S.msg_begin(GW_END + 256 + NBINS * 4));
       uint32_t *gd_tot = gd + GW_END / 4, *gd_hist = gd + (GW_END + 256) / 4;
       if (links) {
-        ReqOp rq{lpar, lab, cur, slices, nullptr, nullptr};
         plan_to_msg(S, rq, m, rpp, gd_tot);
         if (m) {
           k_final_gid_spec<<<grid_for(m, 256), 256, 0, st>>>(lpar, lab, m, gid_own);
@@ -1157,58 +909,23 @@ int classify_sharded_fast(Shard &S, const rk_frags_soa *in, const rk_params &p, 
       throw RK_E_TOO_MANY;
     }
   mop.B = gb;
-  const size_t esz = narrow ? 12 : 16;
-  const bool m_self = P == 1;  // one rank, no halo: the X chunk's member arrays are the rows
+  // one rank, no halo: the X chunk's member arrays are the rows, read in place
   uint32_t mr = 0;
   const void *mem = nullptr;
-  if (m_self) {
+  if (P == 1) {
     mr = m;
   } else {
     PartPlan mpp;
     S.plan_counts(mop, m, mpp, msend);
-    mop.out = S.take<uint8_t>(SN_SMEM, (mpp.total + 1) * esz);
+    mop.out = S.take<uint8_t>(SN_SMEM, (mpp.total + 1) * (narrow ? 12 : 16));
     S.emit(mop, mpp);
-    mem = narrow ? (const void *)xchg<uint3>(S, knownC, mop.out, mpp, mfrom, SL_MEM, &mr)
-                 : (const void *)xchg<uint4>(S, knownC, mop.out, mpp, mfrom, SL_MEM, &mr);
+    const FastExchange ex{S, knownC, mfrom};
+    mem = narrow ? (const void *)ex((const uint3 *)mop.out, mpp, SL_MEM, &mr)
+                 : (const void *)ex((const uint4 *)mop.out, mpp, SL_MEM, &mr);
   }
-  const uint32_t g0 = (uint32_t)gb.b[me], Gl = (uint32_t)(gb.b[me + 1] - gb.b[me]);
-  uint32_t *ogid = S.take<uint32_t>(SL_OGID, mr + 1);
-  uint8_t *orep = S.take<uint8_t>(SL_OREP, mr + 1);
-  uint32_t *oord = S.take<uint32_t>(SL_OORD, mr + 1);
-  uint32_t *sgid = nullptr, *mrow = nullptr, *otag = nullptr, *goffs = nullptr, *tag = nullptr;
-  uint64_t *reckey = nullptr;
-  void *gsort = nullptr;
-  if (mr) {
-    const NwDigits ed = nw_plan(bit_length(Gl ? Gl - 1 : 0), narrow ? 9 : 8);
-    sgid = S.take<uint32_t>(SN_SGID, mr + 1);
-    mrow = S.take<uint32_t>(SN_MROW, mr + 1);
-    reckey = S.take<uint64_t>(SN_KEY, mr + 1);
-    tag = S.take<uint32_t>(SN_TAG, mr + 1);
-    otag = S.take<uint32_t>(SL_OTAG, mr + 1);
-    goffs = S.take<uint32_t>(SN_GOFF, (size_t)Gl + 2);
-    uint4 *t0 = S.take<uint4>(SN_T0, mr + 1), *t1 = S.take<uint4>(SN_T1, mr + 1);
-    uint32_t *mstat = S.take<uint32_t>(SN_STAT, nw_status_words(mr + 1));
-    gsort = S.take<uint8_t>(SL_GSORT, groupsort_scratch_bytes(mr));
-    S.zero(ehist, 4096 * 4);
-    if (m_self) {
-      nw_rec_hist(gid_own, 4, mr, g0, ed, ehist, st);
-      nw_member_sort(reinterpret_cast<const uint4 *>(erk), gid_own, t0, t1, mr, ed, ehist, mstat,
-                     sgid, reckey, tag, mrow, narrow, st);
-    } else {
-      nw_rec_hist(mem, (int)esz, mr, g0, ed, ehist, st);
-      nw_member_sort_recv(mem, narrow, mr, g0, ed, ehist, mstat, t0, t1, sgid, reckey, tag, mrow,
-                          st);
-    }
-    group_offsets(sgid, mr, Gl, goffs, st);
-    // the group-sort tiers on both streams; the depth-limit heap segments
-    // (crafted inputs only) are counted into F[5] and sorted after GE
-    (void)sort_groups_exact(sgid, goffs, Gl, mr, reckey, tag, otag, gsort,
-                            S.scan_scratch(SL_SCAN, mr + Gl + 2), ctx->host + 128, narrow, st,
-                            st2 != st ? st2 : nullptr, ctx->fork, ctx->join, F + 5);
-    emit_result(otag, sgid, goffs, mrow, mr, ogid, orep, oord, st);
-    if (g0) k_add_u32<<<grid_for(mr, 256), 256, 0, st>>>(ogid, mr, g0);
-    S.launched("member order");
-  }
+  // (the depth-limit heap segments -- crafted inputs only -- are counted into
+  // F[5] and sorted after GE)
+  member_order(S, R, mem, mr, gb, narrow, erk, gid_own, F + 5);
   S.alloc_locked = false;
 
   // ---- GE: the error bits and the heap segments ---------------------------------
@@ -1229,10 +946,10 @@ int classify_sharded_fast(Shard &S, const rk_frags_soa *in, const rk_params &p, 
   S.check(err_status(ctx, anyerr4 & ~(uint32_t)ERRB_WIDE_LENGTH));
   int hrc = RK_OK;
   if (heap_me && mr) {  // sorted now, then the result again
-    hrc = sort_groups_heap_deferred(Gl, mr, reckey, tag, otag, gsort, heap_me, ctx->host + 128, st);
+    hrc = sort_groups_heap_deferred(R.Gl, mr, R.reckey, R.tag, R.otag, R.gsort, heap_me,
+                                    ctx->host + 128, st);
     if (!hrc) {
-      emit_result(otag, sgid, goffs, mrow, mr, ogid, orep, oord, st);
-      if (g0) k_add_u32<<<grid_for(mr, 256), 256, 0, st>>>(ogid, mr, g0);
+      emit_members(S, R);
       if (hipGetLastError() != hipSuccess) hrc = RK_E_HIP;
     } else {
       ctx->err = "depth-limit heap segments: buffer allocation failed";
@@ -1244,15 +961,7 @@ int classify_sharded_fast(Shard &S, const rk_frags_soa *in, const rk_params &p, 
     S.agree_errors();
   }
   ss.ms_members = ms_since(tphase);
-  uint64_t ooff = 0, otot = 0;
-  for (uint32_t q = 0; q < P; ++q) otot += mr_all[q], ooff += q < me ? mr_all[q] : 0;
-  out->out_order = oord;
-  out->gid = ogid;
-  out->repval = orep;
-  out->n_out = mr;
-  out->out_offset = ooff;
-  out->n_out_total = otot;
-  out->n_groups = Gtot;
+  set_result(out, R.oord, R.ogid, R.orep, mr, mr_all, me, Gtot);
   for (int k = 0; k < 8; ++k) ctx->sh_fp[k] = new_fp[k];
   return RK_OK;
 }

@@ -26,6 +26,15 @@
 // the single-device record pipeline); otherwise every rank agrees to run the
 // generic driver.  At world size 1 an exchange hands the send block over
 // without a copy.
+//
+// Layout: the kernels and partition ops; the stages of both record drivers
+// (source_rows, rows_to_owners, slice_order, y_to_owners / y_buffers /
+// y_beside_x, lead_in_suffix, solve_x, xhits_follow_y, sweep_y, member_order;
+// local_roots, request_round and the small host helpers sit in rk_shard.hip,
+// where the generic driver uses them too); then the careful driver,
+// classify_sharded_nw, which reads as the sequence of the stages plus what is
+// its own: the readbacks and gathers that size every exchange, and the halo
+// verification loops with their re-resolutions.
 #pragma once
 
 constexpr int RK_SHARD_FALLBACK = 1 << 20;  // not a status: run the generic driver
@@ -346,7 +355,12 @@ __global__ void k_sh_y_results(const uint3 *yr, const uint8_t *code, const uint3
   }
 }
 
-// ---- the driver -----------------------------------------------------------------
+// ---- the stages of both record drivers ------------------------------------------
+// classify_sharded_nw (below) and classify_sharded_fast (rk_shard_fast.h) are
+// sequences of these; RecState (rk_shard.hip) carries what one stage leaves
+// for the next.  A stage that exchanges takes the driver's exchange policy
+// `ex(send, plan, receive slot, &count)`: CarefulExchange here, FastExchange
+// there.
 enum SlotNw : int {
   SN_HIST = SL_COUNT, SN_SROWS, SN_RIN, SN_RA, SN_RB, SN_YOWN, SN_STAT, SN_YSTAT, SN_SHALO, SN_HX,
   SN_HSEL, SN_SY, SN_YR, SN_YA, SN_YB, SN_XCNT, SN_XOFF, SN_XKEY, SN_XENT, SN_XPK, SN_XNBD,
@@ -356,9 +370,8 @@ enum SlotNw : int {
 };
 static_assert(SN_COUNT <= kPoolSlots, "rk_shard.hip kPoolSlots");
 
-// Every record exchange of this driver has its own send slot, so a block that
-// is handed over without a copy at world size 1 is never overwritten by a
-// later exchange.
+// Every record exchange has its own send slot, so a block that is handed over
+// without a copy at world size 1 is never overwritten by a later exchange.
 template <class T>
 T *exchange_nw(Shard &S, const T *send, const PartPlan &pp, int recv_slot, uint32_t *nrecv,
                uint64_t *from = nullptr) {
@@ -371,88 +384,486 @@ T *exchange_nw(Shard &S, const T *send, const PartPlan &pp, int recv_slot, uint3
   }
   return S.exchange<T>(send, pp, recv_slot, nrecv, from);
 }
+struct CarefulExchange {  // sizes by a count gather; an agreement point at every world size
+  Shard &S;
+  template <class T>
+  T *operator()(const T *send, const PartPlan &pp, int slot, uint32_t *nrecv) const {
+    return exchange_nw<T>(S, send, pp, slot, nrecv);
+  }
+};
+
+// A fresh state: the inputs, the digit plans, the route at one rank, and the
+// order / Y / member digit histograms' buffer.
+RecState rec_state(Shard &S, const Geom &geo, const rk_frags_soa *in, const rk_params &p,
+                   bool one_on, bool y_early) {
+  RecState R{};
+  static_cast<Geom &>(R) = geo;
+  R.p = p;
+  R.in = in;
+  R.nl = (uint32_t)in->n;
+  R.f = Frags{in->x_start, in->y_start, in->length, in->strand, R.nl};
+  R.one = one_on && S.P == 1;
+  R.y_early = y_early;
+  R.ad = nw_plan(bit_length(R.vsize - 1));
+  R.yd = nw_plan(bit_length(2ull * R.nby - 1), 9);
+  R.op1 = R.one ? nw_order_split_range(R.nl, 0, R.drop) : NwOrderPlan{};
+  R.ahist = S.take<uint32_t>(SN_HIST, 3 * 4096);
+  R.yhist = R.ahist + 4096, R.ehist = R.ahist + 2 * 4096;
+  return R;
+}
 
 // the largest slice's row count: at one rank the kept rows, else the global
-// histogram's bins between each pair of slice bounds (the bounds lie on bins)
+// histogram's bins between each pair of slice bounds
 static uint64_t slice_max_rows(const std::vector<uint64_t> &gh, const Bounds &sk, uint32_t shift,
                                uint32_t P, uint64_t kept) {
   if (P == 1) return kept;
-  const uint64_t unit = 1ull << shift;
   uint64_t most = 0;
   for (uint32_t q = 0; q < P; ++q) {
-    const uint64_t b0 = (sk.b[q] + unit - 1) >> shift, b1 = (sk.b[q + 1] + unit - 1) >> shift;
-    uint64_t c = 0;
-    for (uint64_t b = b0; b < b1 && b < gh.size(); ++b) c += gh[b];
+    const uint64_t c = bins_in(gh.data(), sk, q, shift);
     most = c > most ? c : most;
   }
   return most;
 }
 
-int classify_sharded_nw(Shard &S, const rk_frags_soa *in, const rk_params &p, uint32_t P,
-                        uint32_t me, uint64_t N, uint64_t row_base, int32_t lead_in,
-                        rk_shard_result *out, std::chrono::steady_clock::time_point t0) {
+// Source rows: keys, checks and histograms.  World size 1 (R.one, rows
+// numbered from 0): the rows are read once, as on one device --
+// k_nw_order_hist takes the checks, the kept count and the order and Y digit
+// histograms (into ahist / yhist) in the place of k_sh_rows, its words in
+// ctrl[32..) ([0] error bits, [1] kept, [3] no pack, [4] longest).  Else
+// k_sh_rows: its words into `words` (ShRowsArgs' layout), the xStart/10 and
+// Y-centre bucket histograms into xhist / yhist (null: not needed).
+void source_rows(Shard &S, const RecState &R, uint32_t *words, uint32_t *xhist, uint32_t *yhist) {
+  if (R.one) {
+    S.zero(R.ahist, 3 * 4096 * 4);
+    S.zero(S.ctrl + 32, 16 * 4);
+    if (R.nl)
+      nw_order_hist(*R.in, R.vsize, R.max_x, R.max_y, R.nby, R.op1.nseg ? R.op1.coarse : R.ad,
+                    R.yd, R.ahist, R.yhist, S.ctrl + 32, S.st);
+  } else if (R.nl) {
+    ShRowsArgs ra{R.f, R.vsize, R.max_x, R.max_y, R.shift, xhist, words};
+    if (yhist) ra.yhist = yhist, ra.yshift = R.yshift;
+    // more blocks when there is no slice histogram to flush (one rank)
+    kt_begin(S.st, KID_SH_ROWKEYS);
+    k_sh_rows<<<grid_for(R.nl, 256, S.P > 1 ? 1024 : 4096), 256, 0, S.st>>>(ra);
+    kt_end(S.st, KID_SH_ROWKEYS, 25.0 * R.nl);
+  }
+  S.launched("source rows");
+}
+
+// every rank's slice size -> the slices' processing-index bounds, this rank's
+// slice
+void set_slices(Shard &S, RecState &R, std::vector<uint64_t> mall) {
+  R.mall = std::move(mall);
+  R.slices = slice_offsets(R.mall);
+  R.m = (uint32_t)R.mall[S.me];
+  R.poff = (uint32_t)R.slices.b[S.me];
+  S.ctx->shard_stats.n_slice = R.m;
+}
+
+// Rows -> slice owners as 16-B records (arrival order = file order).  The
+// bounds lie on histogram bins (or at the end), so this rank's count per owner
+// is a sum of its own bins `mine` (one rank: the kept rows) -- the plan needs
+// no readback.  One rank, no row dropped: the records in row order, or
+// (R.in_place) none at all -- the order sort reads the rows, and the send
+// block is the fine kernel's scratch.
+template <class Ex>
+const uint4 *rows_to_owners(Shard &S, RecState &R, const uint32_t *mine, const Ex &ex,
+                            uint32_t *nrecv) {
+  const uint32_t P = S.P, nl = R.nl;
+  RowOp16 rop{R.f, R.slice_keys, R.drop, (uint32_t)R.row_base, nullptr};
+  PartPlan pp;
+  rop.out = R.srows = S.take<uint4>(SN_SROWS, (size_t)nl + 1);  // room for every row (see plan_counts)
+  R.in_place = R.one && R.kept == nl;
+  if (R.in_place) {
+    S.identity_plan(nl, pp);
+  } else if (P == 1 && R.kept == nl) {
+    S.emit_identity(rop, nl, pp);
+  } else {
+    uint64_t cnt[MAXP] = {};
+    for (uint32_t q = 0; q < P; ++q)
+      cnt[q] = P == 1 ? R.kept : bins_in(mine, R.slice_keys, q, R.shift);
+    S.plan_counts(rop, nl, pp, cnt);
+    S.emit(rop, pp);
+  }
+  return ex(rop.out, pp, SN_RIN, nrecv);
+}
+
+// The slice's processing order (one-sweep passes) and its Y records.  The
+// two-stage order sort (coarse passes, per-segment LDS sort) when the slice's
+// key density suits it: the slice holds m rows over its own key span, and the
+// coarse digits are slice-relative, (key - kbase) >> F, so the segment table
+// covers that span only.  The X axis' chunk width (solve_x) comes from the
+// slice's own rows: the fine kernel then counts the slice's X-chunk entries
+// as it writes the order, and solve_x adds the halo's (when its width comes
+// out the same).
+void slice_order(Shard &S, RecState &R, const uint4 *rin) {
+  const uint32_t m = R.m, me = S.me;
+  hipStream_t st = S.st;
+  // (in place: the order and Y histograms are in, ehist zero; the head-first
+  // Y schedule counts the Y keys itself)
+  if (!R.in_place) S.zero(R.ahist, 3 * 4096 * 4);
+  else if (R.y_early) S.zero(R.yhist, 4096 * 4);
+  uint32_t *astat = S.take<uint32_t>(SN_STAT, nw_status_words(m + 1));
+  uint4 *Ra = R.Ra = S.take<uint4>(SN_RA, m + 1), *Rb = S.take<uint4>(SN_RB, m + 1);
+  uint4 *yown = R.yown = S.take<uint4>(SN_YOWN, (size_t)m * 3 / 4 + 2);  // 12-B records
+  const NwOrderPlan op = R.in_place
+                             ? R.op1
+                             : nw_order_split_range(m, R.slice_keys.b[me], R.slice_keys.b[me + 1]);
+  S.ctx->shard_stats.order_split = op.nseg ? 1u : 0u;
+  R.span = (R.slice_keys.b[me + 1] - R.slice_keys.b[me]) / 10 + 2;
+  NwChunkCounts &own_cc = R.own_cc;
+  own_cc.W = nw_chunk_width(m, (uint32_t)(R.span < R.nbx ? R.span : R.nbx));
+  while ((1u << own_cc.lgW) < own_cc.W) ++own_cc.lgW;
+  own_cc.nch = nw_chunks(R.nbx, own_cc.W);
+  if (m && op.nseg) {
+    uint32_t *chist = S.take<uint32_t>(SN_CHIST, nw_seg_words(m));
+    uint32_t *coff = S.take<uint32_t>(SN_COFF, nw_seg_words(m));
+    own_cc.cnts = S.take<uint32_t>(SN_XCNT0, (size_t)3 * own_cc.nch + 2);
+    if (R.in_place) {  // the rows themselves (op == op1, whose histogram is in)
+      nw_order_sort_split_coarse(*R.in, op, R.ahist, astat, Ra, Rb, chist,
+                                 ZeroRegion{own_cc.cnts, ((size_t)3 * own_cc.nch + 1) * 4},
+                                 R.vsize, st, nullptr);
+      nw_order_sort_split_fine(R.nl, m, R.nby, op, Ra, Rb, yown, R.srows, chist, coff,
+                               S.scan_scratch(SL_PSCAN, (size_t)op.nseg + 1), &own_cc, st);
+    } else {
+      nw_rec_hist(rin, 16, m, op.kbase, op.coarse, R.ahist, st);
+      // rin is read by the first coarse pass only: the fine kernel's scratch
+      nw_order_sort_recs_split(rin, m, R.nby, R.poff, op, R.ahist, astat, Ra, Rb, yown,
+                               const_cast<uint4 *>(rin), chist, coff,
+                               S.scan_scratch(SL_PSCAN, (size_t)op.nseg + 1), &own_cc, st);
+    }
+    R.own_counts = true;
+    S.launched("order sort");
+  } else if (m) {
+    if (R.in_place) {
+      nw_order_sort(*R.in, R.vsize, R.nby, R.ad, R.ahist, astat, Ra, Rb, yown, st);
+    } else {
+      nw_rec_hist(rin, 16, m, 0, R.ad, R.ahist, st);
+      nw_order_sort_recs(rin, m, R.nby, R.poff, R.ad, R.ahist, astat, Ra, Rb, yown, st);
+    }
+    S.launched("order sort");
+  }
+}
+
+// ---- Y records -> Y-range owners (+ halos)
+YOp12 y_op(const RecState &R, uint32_t P) {
+  YOp12 yop{};
+  yop.yrec = reinterpret_cast<const uint3 *>(R.yown);
+  yop.nby = R.nby;
+  yop.P = P;
+  yop.shift = R.yshift;
+  return yop;
+}
+void y_halo_ranges(const Bounds &yb, uint32_t P, uint64_t H, int64_t lo[MAXP], int64_t hi[MAXP]) {
+  for (uint32_t q = 0; q < MAXP; ++q) {
+    lo[q] = q < P ? (int64_t)yb.b[q] - 1 - (int64_t)H : 0;
+    hi[q] = q < P ? (int64_t)yb.b[q + 1] + 1 + (int64_t)H : 0;
+  }
+}
+// the records to the owners of R.yb's ranges; cnt: the per-owner counts (null:
+// counted on the device and read back).  The masks stay cached for the X-hit
+// bytes (xhits_follow_y).
+template <class Ex>
+void y_to_owners(Shard &S, RecState &R, YOp12 &yop, PartPlan &ypp, const uint64_t *cnt,
+                 const Ex &ex) {
+  const uint32_t m = R.m;
+  y_halo_ranges(R.yb, S.P, R.H, yop.lo, yop.hi);
+  if (S.P == 1) {  // one Y range, halos included: every record stays, in order
+    S.identity_plan(m, ypp);
+  } else {
+    ypp.mcache = S.take<uint32_t>(SL_YMASK, m + 1);
+    if (cnt) S.plan_counts(yop, m, ypp, cnt);
+    else S.plan(yop, m, ypp);
+  }
+  // every own record stays here, once: the send layout is the records themselves
+  const bool y_self = ypp.total == m && ypp.cnt[S.me] == m;
+  if (!y_self) {
+    yop.out = S.take<uint3>(SN_SY, ypp.total + 1);
+    S.emit(yop, ypp);
+  }
+  R.yr = ex(y_self ? yop.yrec : yop.out, ypp, SN_YR, &R.ny);
+  S.ctx->shard_stats.y_entries = R.ny;
+}
+// the Y range's buffers (ny records received)
+void y_buffers(Shard &S, RecState &R) {
+  const uint32_t ny = R.ny;
+  R.ylo = R.yb.b[S.me], R.yhi = R.yb.b[S.me + 1];
+  R.ycode = S.take<uint8_t>(SL_YCODE, ny + 1);
+  R.ystate = S.take<uint8_t>(SL_YSTATE, ny + 1);
+  R.ywin = S.take<uint32_t>(SL_YWIN, ny + 1);
+  R.yused = S.take<uint8_t>(SL_YUSED, ny + 1);
+  R.par_l = S.take<uint32_t>(SN_PARL, ny + 1);
+  R.ystat = S.take<uint32_t>(SN_YSTAT, nw_status_words(ny + 1));
+  R.yA = S.take<uint4>(SN_YA, (size_t)ny * 3 / 4 + 2);
+  R.yB = S.take<uint4>(SN_YB, (size_t)ny * 3 / 4 + 2);
+  R.cy.key = S.take<uint32_t>(SN_YKEY, ny + 1);
+  R.cy.ent = S.take<uint32_t>(SN_YENT, ny + 1);
+  R.cy.pk = S.take<uint2>(SN_YPK, ny + 1);
+  R.cy.nbd = S.take<uint8_t>(SN_YNBD, ny + 1);
+  R.cy.state = S.take<uint8_t>(SN_YST, ny + 1);
+  R.ybits = S.take<uint32_t>(SN_XBITS, ny / 32 + 2);
+}
+// the Y sort's passes read the received records (first pass: arrival
+// numbering) and ping-pong through yA / yB; the received array stays whole for
+// the winners' global ids
+void y_sort(Shard &S, const RecState &R, const uint3 *src, uint32_t n, const uint32_t *bits,
+            hipStream_t s, bool head, bool tail) {
+  if (!n) return;
+  if (head) {
+    nw_rec_hist(src, 12, n, 0, R.yd, R.yhist, s);
+    nw_y_sort_head(R.yB, R.yA, n, R.yd, R.yhist, R.ystat, s, true,
+                   reinterpret_cast<const uint4 *>(src));
+  }
+  if (tail)
+    nw_y_sort_tail(R.yB, R.yA, n, R.yd, R.yhist, R.ystat, R.cy, R.nby, R.max_y, bits, s, true,
+                   reinterpret_cast<const uint4 *>(src));
+}
+// Beside X on the second stream: the Y codes (codes) and the Y key histogram
+// (in place: counted by k_nw_order_hist over the same rows).  The Y sort runs
+// after X, as on one device (nw_y_sort_after_x): its first pass carries the
+// X-hit bit in the records, so no pass shares the device with the X axis and
+// the last one needs no lookup.  R.y_early: the round-3 schedule (the head
+// passes beside X, the tail looking the bits up).
+void y_beside_x(Shard &S, const RecState &R, bool codes) {
+  rk_ctx *ctx = S.ctx;
+  const uint32_t ny = R.ny;
+  S.hip(hipEventRecord(ctx->fork, S.st), "fork");
+  S.hip(hipStreamWaitEvent(S.st2, ctx->fork, 0), "fork wait");
+  if (ny && codes) {
+    k_sh_ycode<<<grid_for(ny, 256), 256, 0, S.st2>>>(R.yr, ny, R.nby, R.ylo, R.yhi, R.ycode);
+    S.launched("k_sh_ycode");
+  }
+  if (R.y_early) {
+    y_sort(S, R, R.yr, ny, nullptr, S.st2, true, false);
+    S.launched("Y sort head");
+  } else if (ny && !R.in_place) {
+    nw_rec_hist(R.yr, 12, ny, 0, R.yd, R.yhist, S.st2);
+  }
+  S.hip(hipEventRecord(ctx->join, S.st2), "join");
+}
+
+// ---- X lead-in halo
+// The start of the slice's suffix whose centres can reach a later slice's
+// lead-in, into ctrl[22] (false: no later slice has one, or the slice is empty)
+bool lead_in_suffix(Shard &S, const RecState &R, const uint64_t *thr) {
+  uint64_t thr_min = ~0ull;
+  for (uint32_t g = S.me + 1; g < S.P; ++g) thr_min = thr[g] < thr_min ? thr[g] : thr_min;
+  if (thr_min == ~0ull || !R.m) return false;
+  const uint64_t reach = thr_min * 100;  // centre >= reach is needed
+  const uint64_t half = R.maxlen / 2;
+  const uint64_t key0 = reach > half + 10 ? (reach - half) / 10 - 1 : 0;
+  k_lower_bound16<<<1, 1, 0, S.st>>>(R.Ra, R.m, key0, S.ctrl + 22);
+  S.launched("k_lower_bound16");
+  return true;
+}
+// halo entries from this bucket on are relevant: probed by own queries
+uint64_t relevant_from(const RecState &R, uint32_t me) {
+  const uint64_t bmin_me = R.slice_keys.b[me] / 10;
+  return bmin_me >= 1 ? bmin_me - 1 : 0;
+}
+
+// ---- X axis over [halo ; own] (the X-chunk kernel, no sort)
+void x_buffers(Shard &S, RecState &R, uint32_t G) {
+  R.xg = S.take<uint32_t>(SL_XG, R.m + 1);
+  R.xused = S.take<uint8_t>(SN_XGUSED, G + 1);
+  S.zero(S.ctrl + 6, 4);
+}
+// resolve(axis, scratch, 0): the sweeps, with readbacks (resolve_axis) or
+// queued (resolve_axis_queued); own(xpos, state, par, mx): the own results
+// from the resolved axis (k_sh_x_own, k_sh_x_own_fast, or nw_x_bits at one
+// rank).  par: the parent words (null: a buffer of their own).
+template <class Resolve, class Own>
+void solve_x(Shard &S, RecState &R, const uint4 *halo, uint32_t Gc, uint32_t *par,
+             Resolve &&resolve, Own &&own) {
+  hipStream_t st = S.st;
+  const uint32_t mx = Gc + R.m, nbx = R.nbx;
+  R.Gfin = Gc;  // (the member records sit behind the halo's)
+  R.mx = mx;
+  if (!mx) return;
+  NwChunkCounts cc{};
+  cc.W = nw_chunk_width(mx, (uint32_t)(R.span < nbx ? R.span : nbx));
+  while ((1u << cc.lgW) < cc.W) ++cc.lgW;
+  cc.nch = nw_chunks(nbx, cc.W);
+  cc.cnts = S.take<uint32_t>(SN_XCNT, (size_t)3 * cc.nch + 2);
+  uint32_t *xoff = S.take<uint32_t>(SN_XOFF, (size_t)3 * cc.nch + 2);
+  if (R.own_counts && cc.W == R.own_cc.W) {
+    S.hip(hipMemcpyAsync(cc.cnts, R.own_cc.cnts, ((size_t)3 * cc.nch + 1) * 4,
+                         hipMemcpyDeviceToDevice, st), "counts copy");
+    nw_x_count_add(halo, Gc, cc, st);
+  } else {
+    nw_x_count(R.Ra, mx, cc, st, halo, Gc);
+  }
+  exclusive_scan_u32(cc.cnts, xoff, (size_t)3 * cc.nch + 1,
+                     S.scan_scratch(SL_PSCAN, (size_t)3 * cc.nch + 1), st);
+  Csr cx{};
+  cx.key = S.take<uint32_t>(SN_XKEY, mx + 1);
+  cx.ent = S.take<uint32_t>(SN_XENT, mx + 1);
+  cx.pk = S.take<uint2>(SN_XPK, mx + 1);
+  cx.nbd = S.take<uint8_t>(SN_XNBD, mx + 1);
+  cx.state = S.take<uint8_t>(SN_XSTATE, mx + 1);
+  uint32_t *xpos = S.take<uint32_t>(SN_XPOS, mx + 1);
+  uint4 *erec = S.take<uint4>(SN_EREC, (size_t)mx * 3 / 4 + 2);
+  if (!par) par = S.take<uint32_t>(SN_PAR, mx + 1);
+  nw_x_chunks(R.Ra, mx, nbx, R.max_x, R.maxlen, xoff, cx, xpos, erec, S.ctrl, cc.W, st, halo, Gc);
+  S.launched("X chunks");
+  Axis ax{cx.key, cx.ent, nullptr, nullptr, cx.state, nullptr, par, cx.pk, cx.nbd,
+          S.take<uint32_t>(SL_RLEN, mx), S.take<uint32_t>(SL_RBEG, mx), mx, R.max_x,
+          R.p.len_ratio, R.p.pos_ratio};
+  SweepScratch sc{S.take<uint32_t>(SL_RUNS, runs_scratch_words(mx)),
+                  S.take<uint8_t>(SL_WPEND, mx / 64 + 1), S.take<uint8_t>(SL_RPEND, mx),
+                  S.ctrl + 64, S.ctrl + 4};
+  resolve(ax, sc, 0);
+  own(xpos, cx.state, par, mx);
+}
+
+// ---- Y axis
+// The X-hit bytes follow the Y records (the same plan, the same order) and
+// become the code bits and the Y sort's bitmask.
+template <class Ex>
+void xhits_follow_y(Shard &S, const RecState &R, const YOp12 &yop, const PartPlan &ypp,
+                    const Ex &ex) {
+  YOp12 xop = yop;
+  xop.xg = R.xg;
+  PartPlan xpp;
+  xop.xout = S.take<uint8_t>(SN_SXH, (size_t)ypp.total + 1);
+  if (S.P == 1) {
+    S.emit_identity(xop, R.m, xpp);
+  } else {
+    xpp.mcache = ypp.mcache;
+    xpp.mread = true;
+    S.plan_same(xop, R.m, xpp, ypp);  // the Y records' own selection: counts known
+    S.emit(xop, xpp);
+  }
+  uint32_t n2 = 0;
+  const uint8_t *xh = ex(xop.xout, xpp, SL_YXH, &n2);
+  if (n2 != R.ny) {
+    S.ctx->err = "Y X-hit count mismatch";
+    throw RK_E_INTERNAL;
+  }
+  S.hip(hipStreamWaitEvent(S.st, S.ctx->join, 0), "join wait");
+  if (R.ny) {
+    kt_begin(S.st, KID_SH_MERGE);
+    k_sh_xhit_bits<<<grid_for(R.ny, 256), 256, 0, S.st>>>(xh, R.ny, R.ycode, R.ybits);
+    kt_end(S.st, KID_SH_MERGE, 0.0);
+    S.launched("k_sh_xhit_bits");
+  }
+}
+// the sweeps over the first n entries of the sorted Y axis (resolve as in
+// solve_x, axis 1); par: the parent words
+template <class Resolve>
+void sweep_y(Shard &S, const RecState &R, uint32_t n, uint32_t *par, Resolve &&resolve) {
+  if (!n) return;
+  const Csr &cy = R.cy;
+  Axis ay{cy.key, cy.ent, nullptr, nullptr, cy.state, nullptr, par, cy.pk, cy.nbd,
+          S.take<uint32_t>(SL_RLEN, n), S.take<uint32_t>(SL_RBEG, n), n, R.max_y, R.p.len_ratio,
+          R.p.pos_ratio};
+  ay.par_dev = true;
+  SweepScratch sc{S.take<uint32_t>(SL_RUNS, runs_scratch_words(n)),
+                  S.take<uint8_t>(SL_WPEND, n / 64 + 1), S.take<uint8_t>(SL_RPEND, n),
+                  S.ctrl + 64, S.ctrl + 4};
+  resolve(ay, sc, 1);
+}
+
+// ---- members
+// the member op over the own rows' gids: the X chunk kernel wrote the member
+// records behind the last solve's halo's
+MemOpNw member_op(Shard &S, const RecState &R, const uint32_t *gid_own, uint64_t Gtot,
+                  const uint2 **erk_out) {
+  const uint2 *erk =
+      reinterpret_cast<const uint2 *>(S.take<uint4>(SN_EREC, (size_t)R.mx * 3 / 4 + 2));
+  *erk_out = erk;
+  return MemOpNw{gid_own, erk + R.Gfin, reinterpret_cast<const uint32_t *>(erk + R.mx) + R.Gfin,
+                 {}, bin_shift(Gtot), true, nullptr};
+}
+void emit_members(Shard &S, const RecState &R) {
+  emit_result(R.otag, R.sgid, R.goffs, R.mrow, R.mr, R.ogid, R.orep, R.oord, S.st);
+  if (R.g0) k_add_u32<<<grid_for(R.mr, 256), 256, 0, S.st>>>(R.ogid, R.mr, R.g0);
+}
+// Member order: the gid range gb[me]'s mr members -- received as records
+// (mem), or at one rank without a halo read in place from the X chunk's member
+// arrays erk and the gids (mem null) -- sorted by local gid, then exactly
+// inside every group, and the result.  heap_count: the depth-limit heap
+// segments are counted there and sorted later by the caller (null: here).
+void member_order(Shard &S, RecState &R, const void *mem, uint32_t mr, const Bounds &gb,
+                  bool narrow, const uint2 *erk, const uint32_t *gid_own, uint32_t *heap_count) {
+  rk_ctx *ctx = S.ctx;
+  hipStream_t st = S.st, st2 = S.st2;
+  const uint32_t g0 = R.g0 = (uint32_t)gb.b[S.me];
+  const uint32_t Gl = R.Gl = (uint32_t)(gb.b[S.me + 1] - gb.b[S.me]);
+  R.mr = mr;
+  R.ogid = S.take<uint32_t>(SL_OGID, mr + 1);
+  R.orep = S.take<uint8_t>(SL_OREP, mr + 1);
+  R.oord = S.take<uint32_t>(SL_OORD, mr + 1);
+  if (!mr) return;
+  const NwDigits ed = nw_plan(bit_length(Gl ? Gl - 1 : 0), narrow ? 9 : 8);
+  R.sgid = S.take<uint32_t>(SN_SGID, mr + 1);
+  R.mrow = S.take<uint32_t>(SN_MROW, mr + 1);
+  R.reckey = S.take<uint64_t>(SN_KEY, mr + 1);
+  R.tag = S.take<uint32_t>(SN_TAG, mr + 1);
+  R.otag = S.take<uint32_t>(SL_OTAG, mr + 1);
+  R.goffs = S.take<uint32_t>(SN_GOFF, (size_t)Gl + 2);
+  uint4 *t0 = S.take<uint4>(SN_T0, mr + 1), *t1 = S.take<uint4>(SN_T1, mr + 1);
+  uint32_t *mstat = S.take<uint32_t>(SN_STAT, nw_status_words(mr + 1));
+  R.gsort = S.take<uint8_t>(SL_GSORT, groupsort_scratch_bytes(mr));
+  S.zero(R.ehist, 4096 * 4);
+  if (!mem) {
+    nw_rec_hist(gid_own, 4, mr, g0, ed, R.ehist, st);
+    nw_member_sort(reinterpret_cast<const uint4 *>(erk), gid_own, t0, t1, mr, ed, R.ehist, mstat,
+                   R.sgid, R.reckey, R.tag, R.mrow, narrow, st);
+  } else {
+    nw_rec_hist(mem, narrow ? 12 : 16, mr, g0, ed, R.ehist, st);
+    nw_member_sort_recv(mem, narrow, mr, g0, ed, R.ehist, mstat, t0, t1, R.sgid, R.reckey, R.tag,
+                        R.mrow, st);
+  }
+  group_offsets(R.sgid, mr, Gl, R.goffs, st);
+  // the group-sort tiers on both streams, as in the single-device path
+  const int rc = sort_groups_exact(R.sgid, R.goffs, Gl, mr, R.reckey, R.tag, R.otag, R.gsort,
+                                   S.scan_scratch(SL_SCAN, mr + Gl + 2), ctx->host + 128, narrow,
+                                   st, st2 != st ? st2 : nullptr, ctx->fork, ctx->join, heap_count);
+  if (!heap_count) S.check(rc);
+  emit_members(S, R);
+  S.launched("member order");
+}
+
+// ---- the careful driver -----------------------------------------------------------
+// Every exchange is sized by a device count read back and gathered right
+// before it, the sweeps and the jumping rounds are read back, and a halo that
+// disagrees with its owners is re-resolved.  Returns RK_OK, an error, or
+// RK_SHARD_FALLBACK.
+int classify_sharded_nw(Shard &S, const Geom &geo, const rk_frags_soa *in, const rk_params &p,
+                        bool one_on, bool y_early, uint64_t row_base, rk_shard_result *out,
+                        std::chrono::steady_clock::time_point t0) {
   rk_ctx *ctx = S.ctx;
   rk_shard_stats &ss = ctx->shard_stats;
-  const uint64_t H = lead_in < 0 ? 2 : (uint64_t)lead_in;
-  const uint64_t len_x = p.len_x_hdr + 1, len_y = p.len_y_hdr + 1;  // FragmentsDatabase.cpp:62,65
-  const uint64_t vsize = 1 + len_x / 10;                             // :84
-  const uint64_t max_x = len_x / 100, max_y = len_y / 100;           // SequenceOcupationList.cpp:4
-  const uint32_t nbx = (uint32_t)(max_x + 1), nby = (uint32_t)(max_y + 1);
-  const uint32_t drop = (uint32_t)(vsize - 1);
-  const uint32_t nl = (uint32_t)in->n;
-  hipStream_t st = S.st, st2 = S.st2;
+  const uint32_t P = S.P, me = S.me;
+  hipStream_t st = S.st;
+  RecState R = rec_state(S, geo, in, p, one_on, y_early);
+  R.row_base = row_base;
+  const CarefulExchange ex{S};
+  const auto resolve = [&](const Axis &a, const SweepScratch &sc, int axis) {
+    uint32_t sweeps = 0;
+    S.check(resolve_axis(ctx, a, sc, true, &sweeps));
+    S.max_sweeps[axis] = sweeps > S.max_sweeps[axis] ? sweeps : S.max_sweeps[axis];
+  };
 
   // ---- 1: keys, checks and the slice histogram at the source; every rank
   // agrees on the record layout (or all run the generic driver)
-  Frags f{in->x_start, in->y_start, in->length, in->strand, nl};
-  const uint32_t shift = bin_shift(drop);
-  uint32_t *hist = S.take<uint32_t>(SN_HIST, 3 * 4096);  // later the sorts' digit histograms
-  S.zero(hist, NBINS * 4);
+  S.zero(R.ahist, NBINS * 4);  // (the slice histogram; later the sorts' digit histograms)
   S.zero(S.ctrl + 25, 4);
-  // World size 1 (rows numbered from 0): the rows are read once, as on one
-  // device -- k_nw_order_hist takes the checks, the kept count and the order
-  // and Y digit histograms (into step 3's ahist / yhist) in the place of
-  // k_sh_rows, and when no row is dropped the order sort's first pass reads
-  // the rows themselves (no row records, no record histogram, no Y-record
-  // histogram).  RK_SH_ONE=0: the record route at world size 1 too.
-  static const bool one_on = [] {
-    const char *e = getenv("RK_SH_ONE");
-    return !(e && e[0] == '0');
-  }();
-  static const bool y_early_env = [] {
-    const char *e = getenv("RK_SH_YEARLY");
-    return e && e[0] == '1';
-  }();
-  const bool one = one_on && P == 1 && row_base == 0;
-  const NwDigits ad = nw_plan(bit_length(vsize - 1));
-  const NwDigits yd = nw_plan(bit_length(2ull * nby - 1), 9);
-  const NwOrderPlan op1 = one ? nw_order_split_range(nl, 0, drop) : NwOrderPlan{};
-  if (one) {
-    S.zero(hist, 3 * 4096 * 4);
-    S.zero(S.ctrl + 32, 16 * 4);
-    if (nl)
-      nw_order_hist(*in, vsize, max_x, max_y, nby, op1.nseg ? op1.coarse : ad, yd, hist,
-                    hist + 4096, S.ctrl + 32, st);
-  } else if (nl) {
-    // more blocks when there is no slice histogram to flush (one rank)
-    kt_begin(st, KID_SH_ROWKEYS);
-    k_sh_rows<<<grid_for(nl, 256, P > 1 ? 1024 : 4096), 256, 0, st>>>(
-        ShRowsArgs{f, vsize, max_x, max_y, shift, P > 1 ? hist : nullptr, S.ctrl});
-    kt_end(st, KID_SH_ROWKEYS, 25.0 * nl);
-    S.launched("k_sh_rows");
-  }
+  source_rows(S, R, S.ctrl, P > 1 ? R.ahist : nullptr, nullptr);
   // the error bits (ctrl[0]), the pack flags (ctrl[20..21]), the kept count
   // (ctrl[25]) and the slice histogram in one readback, and the first two with
   // the histogram in one all-gather
   std::vector<uint32_t> flags(41);
   const uint32_t MW = 2 + (P > 1 ? NBINS : 0);  // message words
   std::vector<uint32_t> msg(MW);
-  S.hip(hipMemcpyAsync(flags.data(), S.ctrl, (one ? 41 : 26) * 4, hipMemcpyDeviceToHost, st),
+  S.hip(hipMemcpyAsync(flags.data(), S.ctrl, (R.one ? 41 : 26) * 4, hipMemcpyDeviceToHost, st),
         "d2h");
-  if (P > 1) S.hip(hipMemcpyAsync(msg.data() + 2, hist, NBINS * 4, hipMemcpyDeviceToHost, st), "d2h");
+  if (P > 1)
+    S.hip(hipMemcpyAsync(msg.data() + 2, R.ahist, NBINS * 4, hipMemcpyDeviceToHost, st), "d2h");
   ++S.n_syncs;
   S.hip(hipStreamSynchronize(st), "d2h sync");
-  if (one) {  // k_nw_order_hist's words: [0] error bits, [1] kept, [3] no pack, [4] longest
+  if (R.one) {  // k_nw_order_hist's words in k_sh_rows' layout
     flags[0] = flags[32];
     flags[25] = flags[33];
     flags[20] = flags[35];
@@ -462,304 +873,91 @@ int classify_sharded_nw(Shard &S, const rk_frags_soa *in, const rk_params &p, ui
   msg[1] = flags[20] | (flags[21] << 1);
   std::vector<uint32_t> allm((size_t)P * MW);
   S.allgather(msg.data(), allm.data(), MW * 4);
-  uint32_t anyerr = 0, nopack = 0, maxlen = 0;
+  uint32_t anyerr = 0, nopack = 0;
   std::vector<uint64_t> gh(NBINS, 0);
   for (uint32_t q = 0; q < P; ++q) {
     const uint32_t *mq = allm.data() + (size_t)q * MW;
     anyerr |= mq[0];
     nopack |= mq[1] & 1u;
-    maxlen = (mq[1] >> 1) > maxlen ? (mq[1] >> 1) : maxlen;
+    R.maxlen = (mq[1] >> 1) > R.maxlen ? (mq[1] >> 1) : R.maxlen;
     if (P > 1)
       for (uint32_t b = 0; b < NBINS; ++b) gh[b] += mq[2 + b];
   }
   S.check(err_status(ctx, anyerr & ~(uint32_t)ERRB_WIDE_LENGTH));
   if (nopack) return RK_SHARD_FALLBACK;
-  const uint32_t *mine = msg.data() + 2;  // this rank's own bins (P > 1)
-  const Bounds slice_keys = split_bounds(gh, shift, drop, P);
+  R.kept = flags[25];
+  R.slice_keys = split_bounds(gh, R.shift, R.drop, P);
   // the one-sweep passes' status words carry a 30-bit count (SW_VAL,
   // rk_onesweep.h), as the single-device record pipeline's bound n < 2^30
   // (record_eligible): a slice of 2^30 or more rows takes the generic driver.
   // Every rank sees the same global histogram (the kept count at one rank), so
   // the decision is agreed
-  if (slice_max_rows(gh, slice_keys, shift, P, flags[25]) >= (1ull << 30)) return RK_SHARD_FALLBACK;
+  if (slice_max_rows(gh, R.slice_keys, R.shift, P, R.kept) >= (1ull << 30))
+    return RK_SHARD_FALLBACK;
 
-  // ---- 2: rows -> slice owners as 16-B records (arrival order = file order);
-  // the bounds lie on histogram bins (or at the end), so this rank's count per
-  // owner is a sum of its own bins -- the plan needs no readback
-  RowOp16 rop{f, slice_keys, drop, (uint32_t)row_base, nullptr};
-  PartPlan pp;
-  rop.out = S.take<uint4>(SN_SROWS, (size_t)nl + 1);  // room for every row (see plan_counts)
-  // (fast: step 3 reads the rows, rop.out is the fine kernel's scratch)
-  const bool fast = one && flags[25] == nl;
-  if (fast) {
-    S.identity_plan(nl, pp);
-  } else if (P == 1 && flags[25] == nl) {  // one rank, no row dropped: the records in row order
-    S.emit_identity(rop, nl, pp);
-  } else {
-    uint64_t cnt[MAXP] = {};
-    if (P == 1) {
-      cnt[0] = flags[25];
-    } else {
-      const uint64_t unit = 1ull << shift;
-      for (uint32_t q = 0; q < P; ++q) {
-        const uint64_t b0 = (slice_keys.b[q] + unit - 1) >> shift,
-                       b1 = (slice_keys.b[q + 1] + unit - 1) >> shift;
-        for (uint64_t b = b0; b < b1 && b < NBINS; ++b) cnt[q] += mine[b];
-      }
-    }
-    S.plan_counts(rop, nl, pp, cnt);
-    S.emit(rop, pp);
-  }
+  // ---- 2: rows -> slice owners; every rank's slice size is known from the
+  // exchange's count all-gather
   uint32_t m = 0;
-  const uint4 *rin = exchange_nw<uint4>(S, rop.out, pp, SN_RIN, &m);
-  // every rank's slice size: known from the exchange's count all-gather
-  std::vector<uint64_t> mall(S.last_recv, S.last_recv + P);
-  uint64_t poff64 = 0, M = 0;
-  for (uint32_t q = 0; q < P; ++q) M += mall[q], poff64 += q < me ? mall[q] : 0;
-  const uint32_t poff = (uint32_t)poff64;
-  Bounds slices{};
-  slices.P = P;
-  for (uint32_t q = 0, acc = 0; q <= MAXP; ++q) {
-    slices.b[q] = acc;
-    if (q < P) acc += (uint32_t)mall[q];
-  }
-  ss.n_slice = m;
+  const uint4 *rin = rows_to_owners(S, R, msg.data() + 2, ex, &m);
+  set_slices(S, R, std::vector<uint64_t>(S.last_recv, S.last_recv + P));
 
-  // ---- 3: the slice's processing order (one-sweep passes), its Y records
-  uint32_t *ahist = S.take<uint32_t>(SN_HIST, 3 * 4096);  // order / Y / member digit histograms
-  uint32_t *yhist = ahist + 4096, *ehist = ahist + 2 * 4096;
-  if (!fast) S.zero(ahist, 3 * 4096 * 4);  // (fast: the order and Y ones are in, ehist zero)
-  else if (y_early_env) S.zero(yhist, 4096 * 4);  // (that schedule counts the Y keys itself)
-  const size_t sw = nw_status_words(m + 1);
-  uint32_t *astat = S.take<uint32_t>(SN_STAT, sw);
-  uint4 *Ra = S.take<uint4>(SN_RA, m + 1), *Rb = S.take<uint4>(SN_RB, m + 1);
-  uint4 *yown = S.take<uint4>(SN_YOWN, (size_t)m * 3 / 4 + 2);  // 12-B records
-  // the two-stage order sort (coarse passes, per-segment LDS sort) when the
-  // slice's key density suits it: the slice holds m rows over its own key
-  // span, and the coarse digits are slice-relative, (key - kbase) >> F, so the
-  // segment table covers that span only
-  const NwOrderPlan op = fast ? op1 : nw_order_split_range(m, slice_keys.b[me], slice_keys.b[me + 1]);
-  ss.order_split = op.nseg ? 1u : 0u;
-  // the X axis' chunk width (step 6) from the slice's own rows: the fine
-  // kernel then counts the slice's X-chunk entries as it writes the order, and
-  // step 6 adds the halo's (when its width comes out the same)
-  const uint64_t span = (slice_keys.b[me + 1] - slice_keys.b[me]) / 10 + 2;
-  NwChunkCounts own_cc{};
-  own_cc.W = nw_chunk_width(m, (uint32_t)(span < nbx ? span : nbx));
-  while ((1u << own_cc.lgW) < own_cc.W) ++own_cc.lgW;
-  own_cc.nch = nw_chunks(nbx, own_cc.W);
-  bool own_counts = false;
-  if (m && op.nseg) {
-    uint32_t *chist = S.take<uint32_t>(SN_CHIST, nw_seg_words(m));
-    uint32_t *coff = S.take<uint32_t>(SN_COFF, nw_seg_words(m));
-    own_cc.cnts = S.take<uint32_t>(SN_XCNT0, (size_t)3 * own_cc.nch + 2);
-    if (fast) {  // the rows themselves (op == op1, whose histogram is in)
-      nw_order_sort_split_coarse(*in, op, ahist, astat, Ra, Rb, chist,
-                                 ZeroRegion{own_cc.cnts, ((size_t)3 * own_cc.nch + 1) * 4}, vsize,
-                                 st, nullptr);
-      nw_order_sort_split_fine(nl, m, nby, op, Ra, Rb, yown, rop.out, chist, coff,
-                               S.scan_scratch(SL_PSCAN, (size_t)op.nseg + 1), &own_cc, st);
-    } else {
-      nw_rec_hist(rin, 16, m, op.kbase, op.coarse, ahist, st);
-      // rin is read by the first coarse pass only: the fine kernel's scratch
-      nw_order_sort_recs_split(rin, m, nby, poff, op, ahist, astat, Ra, Rb, yown,
-                               const_cast<uint4 *>(rin), chist, coff,
-                               S.scan_scratch(SL_PSCAN, (size_t)op.nseg + 1), &own_cc, st);
-    }
-    own_counts = true;
-    S.launched("order sort");
-  } else if (m) {
-    if (fast) {
-      nw_order_sort(*in, vsize, nby, ad, ahist, astat, Ra, Rb, yown, st);
-    } else {
-      nw_rec_hist(rin, 16, m, 0, ad, ahist, st);
-      nw_order_sort_recs(rin, m, nby, poff, ad, ahist, astat, Ra, Rb, yown, st);
-    }
-    S.launched("order sort");
-  }
+  // ---- 3: the slice's processing order, its Y records
+  slice_order(S, R, rin);
   ss.ms_ingress = ms_since(t0);
 
-  // ---- 4: Y records -> Y-range owners (+ halos); their sort starts on the
-  // second stream while X resolves
+  // ---- 4: Y records -> Y-range owners (+ halos), their ranges from the
+  // global histogram of the records' buckets; beside X on the second stream:
+  // the Y codes and the Y key histogram (or the Y sort's head passes)
   const auto ty = std::chrono::steady_clock::now();
-  YOp12 yop{};
-  yop.yrec = reinterpret_cast<const uint3 *>(yown);
-  yop.nby = nby;
-  yop.P = P;
-  yop.shift = bin_shift(nby);
-  const Bounds yb = split_bounds(P > 1 ? global_hist(S, yop, m) : std::vector<uint64_t>(NBINS, 0),
-                                 yop.shift, nby, P);
-  for (uint32_t q = 0; q < MAXP; ++q) {
-    yop.lo[q] = q < P ? (int64_t)yb.b[q] - 1 - (int64_t)H : 0;
-    yop.hi[q] = q < P ? (int64_t)yb.b[q + 1] + 1 + (int64_t)H : 0;
-  }
+  YOp12 yop = y_op(R, P);
+  R.yb = split_bounds(P > 1 ? global_hist(S, yop, m) : std::vector<uint64_t>(NBINS, 0), R.yshift,
+                      R.nby, P);
   PartPlan ypp;
-  if (P == 1) {  // one Y range, halos included: every record stays, in order
-    S.identity_plan(m, ypp);
-  } else {
-    ypp.mcache = S.take<uint32_t>(SL_YMASK, m + 1);  // the X-hit bytes follow the same masks
-    S.plan(yop, m, ypp);
-  }
-  // every own record stays here, once: the send layout is the records themselves
-  const bool y_self = ypp.total == m && ypp.cnt[me] == m;
-  if (!y_self) {
-    yop.out = S.take<uint3>(SN_SY, ypp.total + 1);
-    S.emit(yop, ypp);
-  }
-  uint32_t ny = 0;
-  const uint3 *yr = exchange_nw<uint3>(S, y_self ? yop.yrec : yop.out, ypp, SN_YR, &ny);
-  ss.y_entries = ny;
+  y_to_owners(S, R, yop, ypp, nullptr, ex);
   // the Y ranges (+ halos) received: the same 30-bit bound on every rank's
   // sort (every rank knows every rank's count from the exchange)
   S.check_recv_below(1u << 30, RK_E_TOO_MANY, "a Y range of 2^30 or more records");
-  const uint64_t ylo = yb.b[me], yhi = yb.b[me + 1];
-  uint8_t *ycode = S.take<uint8_t>(SL_YCODE, ny + 1);
-  uint8_t *ystate = S.take<uint8_t>(SL_YSTATE, ny + 1);
-  uint32_t *ywin = S.take<uint32_t>(SL_YWIN, ny + 1);
-  uint8_t *yused = S.take<uint8_t>(SL_YUSED, ny + 1);
-  uint32_t *par_l = S.take<uint32_t>(SN_PARL, ny + 1);
-  uint32_t *ystat = S.take<uint32_t>(SN_YSTAT, nw_status_words(ny + 1));
-  uint4 *yA = S.take<uint4>(SN_YA, (size_t)ny * 3 / 4 + 2), *yB = S.take<uint4>(SN_YB, (size_t)ny * 3 / 4 + 2);
-  Csr cy{};
-  cy.key = S.take<uint32_t>(SN_YKEY, ny + 1);
-  cy.ent = S.take<uint32_t>(SN_YENT, ny + 1);
-  cy.pk = S.take<uint2>(SN_YPK, ny + 1);
-  cy.nbd = S.take<uint8_t>(SN_YNBD, ny + 1);
-  cy.state = S.take<uint8_t>(SN_YST, ny + 1);
-  uint32_t *ybits = S.take<uint32_t>(SN_XBITS, ny / 32 + 2);
-  // the Y sort's passes read the received records (first pass: arrival
-  // numbering) and ping-pong through yA / yB; the received array stays whole
-  // for the winners' global ids
-  auto y_sort = [&](const uint3 *src, uint32_t n, const uint32_t *bits, hipStream_t s,
-                    bool head, bool tail) {
-    if (!n) return;
-    if (head) {
-      nw_rec_hist(src, 12, n, 0, yd, yhist, s);
-      nw_y_sort_head(yB, yA, n, yd, yhist, ystat, s, true, reinterpret_cast<const uint4 *>(src));
-    }
-    if (tail)
-      nw_y_sort_tail(yB, yA, n, yd, yhist, ystat, cy, nby, max_y, bits, s, true,
-                     reinterpret_cast<const uint4 *>(src));
-  };
-  // The Y sort runs after X, as on one device (nw_y_sort_after_x): its first
-  // pass carries the X-hit bit in the records, so no pass shares the device
-  // with the X axis and the last one needs no lookup.  Beside X on the second
-  // stream: the Y codes and the Y key histogram.  RK_SH_YEARLY=1: the round-3
-  // schedule (the head passes beside X, the tail looking the bits up)
-  static const bool y_early = [] {
-    const char *e = getenv("RK_SH_YEARLY");
-    return e && e[0] == '1';
-  }();
-  hipStream_t sy = st2;
-  S.hip(hipEventRecord(ctx->fork, st), "fork");
-  S.hip(hipStreamWaitEvent(st2, ctx->fork, 0), "fork wait");
-  if (ny) {
-    k_sh_ycode<<<grid_for(ny, 256), 256, 0, sy>>>(yr, ny, nby, ylo, yhi, ycode);
-    S.launched("k_sh_ycode");
-  }
-  if (y_early) {
-    y_sort(yr, ny, nullptr, sy, true, false);
-    S.launched("Y sort head");
-  } else if (ny && !fast) {  // (fast: counted by k_nw_order_hist over the same rows)
-    nw_rec_hist(yr, 12, ny, 0, yd, yhist, sy);
-  }
-  S.hip(hipEventRecord(ctx->join, st2), "join");
+  y_buffers(S, R);
+  const uint32_t ny = R.ny;
+  y_beside_x(S, R, true);
   ss.ms_y = ms_since(ty);
 
   // ---- 5: X lead-in halo from earlier slices (16-B records, global ids)
   const auto tx = std::chrono::steady_clock::now();
   GhostOp16 gop{};
-  gop.R = Ra;
+  gop.R = R.Ra;
   gop.P = P;
   gop.me = me;
-  gop.poff = poff;
-  for (uint32_t g = 0; g < MAXP; ++g) {
-    gop.thr[g] = ~0ull;
-    if (g < P && mall[g]) {
-      const uint64_t bmin = slice_keys.b[g] / 10;  // xStart >= 10*key, centre >= xStart
-      gop.thr[g] = bmin >= 1 + H ? bmin - 1 - H : 0;
-    }
-  }
-  {  // the suffix of the slice whose centres can reach a later slice's lead-in
-    uint64_t thr_min = ~0ull;
-    for (uint32_t g = me + 1; g < P; ++g) thr_min = gop.thr[g] < thr_min ? gop.thr[g] : thr_min;
-    uint32_t k0 = m;
-    if (thr_min != ~0ull && m) {
-      const uint64_t reach = thr_min * 100;  // centre >= reach is needed
-      const uint64_t half = maxlen / 2;
-      const uint64_t key0 = reach > half + 10 ? (reach - half) / 10 - 1 : 0;
-      k_lower_bound16<<<1, 1, 0, st>>>(Ra, m, key0, S.ctrl + 22);
-      S.launched("k_lower_bound16");
-      k0 = S.read1(S.ctrl + 22);
-    }
-    gop.base = k0;
-  }
+  gop.poff = R.poff;
+  lead_in_thresholds(gop.thr, R.mall, R.slice_keys, R.H);
+  gop.base = lead_in_suffix(S, R, gop.thr) ? S.read1(S.ctrl + 22) : m;
   const uint32_t nsuf = m - gop.base;
-  const uint64_t bmin_me = slice_keys.b[me] / 10;
-  const uint64_t rel_x = bmin_me >= 1 ? bmin_me - 1 : 0;  // relevant: probed by own queries
+  PartPlan pp;
   if (nsuf) S.plan(gop, nsuf, pp);
   else S.zero_plan(0, pp);  // no row can reach a later slice: nothing to send
   gop.out = S.take<uint4>(SN_SHALO, pp.total + 1);
   if (nsuf) S.emit(gop, pp);
   uint32_t G = 0;
-  const uint4 *hx = exchange_nw<uint4>(S, gop.out, pp, SN_HX, &G);
+  const uint4 *hx = ex(gop.out, pp, SN_HX, &G);
   ss.x_ghosts = G;
 
-  // ---- 6: X axis over [halo ; own] (the X-chunk kernel, no sort)
-  uint32_t *xg = S.take<uint32_t>(SL_XG, m + 1);
-  uint8_t *xused = S.take<uint8_t>(SN_XGUSED, G + 1);
-  uint32_t Gfin = 0;            // the halo of the last X solve
-  const uint4 *hfin = nullptr;  // (its records: member records sit behind it)
-  auto solve_x = [&](const uint4 *halo, uint32_t Gc) {
-    const uint32_t mx = Gc + m;
-    Gfin = Gc;
-    hfin = halo;
-    if (!mx) return;
-    NwChunkCounts cc{};
-    cc.W = nw_chunk_width(mx, (uint32_t)(span < nbx ? span : nbx));
-    while ((1u << cc.lgW) < cc.W) ++cc.lgW;
-    cc.nch = nw_chunks(nbx, cc.W);
-    cc.cnts = S.take<uint32_t>(SN_XCNT, (size_t)3 * cc.nch + 2);
-    uint32_t *xoff = S.take<uint32_t>(SN_XOFF, (size_t)3 * cc.nch + 2);
-    if (own_counts && cc.W == own_cc.W) {
-      (void)hipMemcpyAsync(cc.cnts, own_cc.cnts, ((size_t)3 * cc.nch + 1) * 4,
-                           hipMemcpyDeviceToDevice, st);
-      nw_x_count_add(halo, Gc, cc, st);
-    } else {
-      nw_x_count(Ra, mx, cc, st, halo, Gc);
-    }
-    exclusive_scan_u32(cc.cnts, xoff, (size_t)3 * cc.nch + 1,
-                       S.scan_scratch(SL_PSCAN, (size_t)3 * cc.nch + 1), st);
-    Csr cx{};
-    cx.key = S.take<uint32_t>(SN_XKEY, mx + 1);
-    cx.ent = S.take<uint32_t>(SN_XENT, mx + 1);
-    cx.pk = S.take<uint2>(SN_XPK, mx + 1);
-    cx.nbd = S.take<uint8_t>(SN_XNBD, mx + 1);
-    cx.state = S.take<uint8_t>(SN_XSTATE, mx + 1);
-    uint32_t *xpos = S.take<uint32_t>(SN_XPOS, mx + 1);
-    uint4 *erec = S.take<uint4>(SN_EREC, (size_t)mx * 3 / 4 + 2);
-    uint32_t *par = S.take<uint32_t>(SN_PAR, mx + 1);
-    nw_x_chunks(Ra, mx, nbx, max_x, maxlen, xoff, cx, xpos, erec, S.ctrl, cc.W, st, halo, Gc);
-    S.launched("X chunks");
-    Axis ax{cx.key, cx.ent, nullptr, nullptr, cx.state, nullptr, par, cx.pk, cx.nbd,
-            S.take<uint32_t>(SL_RLEN, mx), S.take<uint32_t>(SL_RBEG, mx), mx, max_x,
-            p.len_ratio, p.pos_ratio};
-    SweepScratch sc{S.take<uint32_t>(SL_RUNS, runs_scratch_words(mx)),
-                    S.take<uint8_t>(SL_WPEND, mx / 64 + 1), S.take<uint8_t>(SL_RPEND, mx),
-                    S.ctrl + 64, S.ctrl + 4};
-    uint32_t sweeps = 0;
-    S.check(resolve_axis(ctx, ax, sc, true, &sweeps));
-    S.max_sweeps[0] = sweeps > S.max_sweeps[0] ? sweeps : S.max_sweeps[0];
-    kt_begin(st, KID_SH_XOWN);
-    k_sh_x_own<<<grid_for(mx, 256), 256, 0, st>>>(xpos, cx.state, par, halo, Gc, m, poff, xg,
-                                                  xused);
-    kt_end(st, KID_SH_XOWN, 0.0);
-    S.launched("k_sh_x_own");
+  // ---- 6: X axis over [halo ; own]
+  x_buffers(S, R, G);
+  uint32_t *xg = R.xg;
+  const auto x_own = [&](const uint4 *halo, uint32_t Gc) {
+    return [&, halo, Gc](const uint32_t *xpos, const uint8_t *state, const uint32_t *par,
+                         uint32_t mx) {
+      kt_begin(st, KID_SH_XOWN);
+      k_sh_x_own<<<grid_for(mx, 256), 256, 0, st>>>(xpos, state, par, halo, Gc, m, R.poff, xg,
+                                                    R.xused);
+      kt_end(st, KID_SH_XOWN, 0.0);
+      S.launched("k_sh_x_own");
+    };
   };
-  S.zero(S.ctrl + 6, 4);
-  solve_x(hx, G);
+  solve_x(S, R, hx, G, nullptr, resolve, x_own(hx, G));
   // verify the relevant halo against its owners' decisions (one rank: there
   // are no later slices, so no halo was sent or received)
+  const uint64_t rel_x = relevant_from(R, me);
   for (; P > 1;) {
     ++ss.x_rounds;
     if (ss.x_rounds > P + 2) {
@@ -780,7 +978,7 @@ int classify_sharded_nw(Shard &S, const rk_frags_soa *in, const rk_params &p, ui
     }
     S.zero(S.ctrl + 2, 4);
     if (G) {
-      k_cmp_x16<<<grid_for(G, 256, 1024), 256, 0, st>>>(hx, G, rel_x, xused, xown, S.ctrl + 2);
+      k_cmp_x16<<<grid_for(G, 256, 1024), 256, 0, st>>>(hx, G, rel_x, R.xused, xown, S.ctrl + 2);
       S.launched("k_cmp_x16");
     }
     const uint32_t mism = S.read1(S.ctrl + 2);
@@ -795,91 +993,53 @@ int classify_sharded_nw(Shard &S, const rk_frags_soa *in, const rk_params &p, ui
       S1.plan(sel, G, sp);
       sel.out = S.take<uint4>(SN_HSEL, sp.total + 1);
       S1.emit(sel, sp);
-      solve_x(sel.out, (uint32_t)sp.total);
-      S.hip(hipMemcpyAsync(xused, xown, G, hipMemcpyDeviceToDevice, st), "xused copy");
+      solve_x(S, R, sel.out, (uint32_t)sp.total, nullptr, resolve,
+              x_own(sel.out, (uint32_t)sp.total));
+      S.hip(hipMemcpyAsync(R.xused, xown, G, hipMemcpyDeviceToDevice, st), "xused copy");
     }
   }
   ss.ms_x = ms_since(tx);
 
-  // ---- 7: the X-hit bytes follow the Y records (same plan, same order); the
-  // Y sort's last pass writes the CSR with the states
+  // ---- 7: the X-hit bytes follow the Y records; the Y sort's last pass
+  // writes the CSR with the states
   const auto ty2 = std::chrono::steady_clock::now();
-  {
-    YOp12 xop = yop;
-    xop.xg = xg;
-    PartPlan xpp;
-    xop.xout = S.take<uint8_t>(SN_SXH, (size_t)ypp.total + 1);
-    if (P == 1) {
-      S.emit_identity(xop, m, xpp);
-    } else {
-      xpp.mcache = ypp.mcache;
-      xpp.mread = true;
-      S.plan_same(xop, m, xpp, ypp);  // the Y records' own selection: counts known
-      S.emit(xop, xpp);
-    }
-    uint32_t n2 = 0;
-    const uint8_t *xh = exchange_nw<uint8_t>(S, xop.xout, xpp, SL_YXH, &n2);
-    if (n2 != ny) {
-      ctx->err = "Y X-hit count mismatch";
-      throw RK_E_INTERNAL;
-    }
-    S.hip(hipStreamWaitEvent(st, ctx->join, 0), "join wait");
-    if (ny) {
-      kt_begin(st, KID_SH_MERGE);
-      k_sh_xhit_bits<<<grid_for(ny, 256), 256, 0, st>>>(xh, ny, ycode, ybits);
-      kt_end(st, KID_SH_MERGE, 0.0);
-      S.launched("k_sh_xhit_bits");
-    }
-  }
-  auto sweep_y = [&](uint32_t n) {
-    if (!n) return;
-    Axis ay{cy.key, cy.ent, nullptr, nullptr, cy.state, nullptr, par_l, cy.pk, cy.nbd,
-            S.take<uint32_t>(SL_RLEN, n), S.take<uint32_t>(SL_RBEG, n), n, max_y, p.len_ratio,
-            p.pos_ratio};
-    ay.par_dev = true;
-    SweepScratch sc{S.take<uint32_t>(SL_RUNS, runs_scratch_words(n)),
-                    S.take<uint8_t>(SL_WPEND, n / 64 + 1), S.take<uint8_t>(SL_RPEND, n),
-                    S.ctrl + 64, S.ctrl + 4};
-    uint32_t sweeps = 0;
-    S.check(resolve_axis(ctx, ay, sc, true, &sweeps));
-    S.max_sweeps[1] = sweeps > S.max_sweeps[1] ? sweeps : S.max_sweeps[1];
-  };
-  auto y_results = [&](const uint32_t *ymap, uint32_t c) {
+  xhits_follow_y(S, R, yop, ypp, ex);
+  const auto y_results = [&](const uint32_t *ymap, uint32_t c) {
     if (!c) return;
     kt_begin(st, KID_SH_YRES);
-    k_sh_y_results<<<grid_for(c, 256), 256, 0, st>>>(yr, ycode, ymap, c, par_l, ystate, ywin,
-                                                      poff, m, xg);
+    k_sh_y_results<<<grid_for(c, 256), 256, 0, st>>>(R.yr, R.ycode, ymap, c, R.par_l, R.ystate,
+                                                      R.ywin, R.poff, m, xg);
     kt_end(st, KID_SH_YRES, 0.0);
     S.launched("k_sh_y_results");
   };
-  if (y_early) {
-    y_sort(yr, ny, ybits, st, false, true);
+  if (R.y_early) {
+    y_sort(S, R, R.yr, ny, R.ybits, st, false, true);
   } else if (ny) {
-    nw_y_sort_after_x(yB, yA, ny, yd, yhist, ystat, cy, nby, max_y, ybits, st,
-                      reinterpret_cast<const uint4 *>(yr));
+    nw_y_sort_after_x(R.yB, R.yA, ny, R.yd, R.yhist, R.ystat, R.cy, R.nby, R.max_y, R.ybits, st,
+                      reinterpret_cast<const uint4 *>(R.yr));
   }
   S.launched("Y sort");
-  sweep_y(ny);
+  sweep_y(S, R, ny, R.par_l, resolve);
   y_results(nullptr, ny);
   // a fixed-halo re-resolution: the selected records sorted again on stream 1
-  auto solve_y = [&](const uint32_t *ymap, uint32_t c) {
+  const auto solve_y = [&](const uint32_t *ymap, uint32_t c) {
     if (!c) return;
     uint3 *ysel = S.take<uint3>(SN_YSEL, c + 1);
-    k_sh_ysel<<<grid_for(c, 256), 256, 0, st>>>(yr, ycode, ymap, c, ysel, ybits);
+    k_sh_ysel<<<grid_for(c, 256), 256, 0, st>>>(R.yr, R.ycode, ymap, c, ysel, R.ybits);
     S.launched("k_sh_ysel");
-    S.zero(yhist, 4096 * 4);
-    y_sort(ysel, c, ybits, st, true, true);
-    sweep_y(c);
+    S.zero(R.yhist, 4096 * 4);
+    y_sort(S, R, ysel, c, R.ybits, st, true, true);
+    sweep_y(S, R, c, R.par_l, resolve);
     y_results(ymap, c);
   };
-  const RelOp relop{ycode, ylo ? owner_of_host(yb, ylo - 1) : 0u,
-                    yhi < nby ? owner_of_host(yb, yhi) : 0u, nullptr};
-  verify_y_halo(S, relop, ycode, ystate, yused, yb, ny, solve_y);
+  const RelOp relop{R.ycode, R.ylo ? owner_of_host(R.yb, R.ylo - 1) : 0u,
+                    R.yhi < R.nby ? owner_of_host(R.yb, R.yhi) : 0u, nullptr};
+  verify_y_halo(S, relop, R.ycode, R.ystate, R.yused, R.yb, ny, solve_y);
   ss.ms_y += ms_since(ty2);
 
   // ---- 8: parents back to the slice owners; roots; gids
   const auto tr = std::chrono::steady_clock::now();
-  ParOp12 pop{yr, ycode, slices, ywin, me, nullptr};
+  ParOp12 pop{R.yr, R.ycode, R.slices, R.ywin, me, nullptr};
   if (P == 1) S.zero_plan(ny, pp);  // every parent is local (written by k_sh_y_results)
   else S.plan(pop, ny, pp);
   pop.out = S.take<ParRec>(SL_SEND, pp.total + 1);
@@ -887,98 +1047,49 @@ int classify_sharded_nw(Shard &S, const rk_frags_soa *in, const rk_params &p, ui
   uint32_t npar = 0;
   const ParRec *prr = S.exchange<ParRec>(pop.out, pp, SL_PR, &npar);
   uint64_t Gtot = 0;
-  const uint32_t *gid_own = resolve_roots(S, xg, prr, npar, m, poff, slices, &Gtot);
+  const uint32_t *gid_own = resolve_roots(S, xg, prr, npar, m, R.poff, R.slices, &Gtot);
   ss.ms_roots = ms_since(tr);
 
   // ---- 9: members -> gid-range owners; exact in-group order; emit
   const auto tm = std::chrono::steady_clock::now();
-  bool narrow = true;  // every sort key fits 32 bits (the X-chunk kernel's flag)
-  const uint32_t mx = Gfin + m;
-  const uint2 *erk = reinterpret_cast<const uint2 *>(S.take<uint4>(SN_EREC, (size_t)mx * 3 / 4 + 2));
-  MemOpNw mop{gid_own, erk + Gfin, reinterpret_cast<const uint32_t *>(erk + mx) + Gfin,
-              {}, bin_shift(Gtot), true, nullptr};
-  (void)hfin;
-  // the gid histogram and the wide-key flags in one readback and one all-gather
+  const uint2 *erk = nullptr;
+  MemOpNw mop = member_op(S, R, gid_own, Gtot, &erk);
+  // the gid histogram and the wide-key flags (the X-chunk kernel's) in one
+  // readback and one all-gather
   std::vector<uint32_t> wide;
   std::vector<uint64_t> ghist(NBINS, 0);
   if (P > 1) ghist = global_hist(S, mop, m, {S.ctrl + 6}, &wide);
   else wide = S.gather1<uint32_t>(S.read1(S.ctrl + 6));
+  bool narrow = true;  // every sort key fits 32 bits
   for (uint32_t w : wide) narrow &= w == 0;
   mop.narrow = narrow;
   const Bounds gb = split_bounds(ghist, mop.shift, Gtot, P);
   mop.B = gb;
-  const size_t esz = narrow ? 12 : 16;
   // one rank: every member stays here and the X chunk's member arrays are
   // exactly the own rows (no halo): the member sort reads them in place, as on
   // one device (no plan needed)
-  const bool m_self = P == 1 && Gfin == 0;
-  if (!m_self) S.plan(mop, m, pp);
-  if (!m_self) {
-    mop.out = S.take<uint8_t>(SN_SMEM, (pp.total + 1) * esz);
-    S.emit(mop, pp);
-  }
+  const bool m_self = P == 1 && R.Gfin == 0;
   uint32_t mr = 0;
   const void *mem = nullptr;
   if (m_self) {
     S.agree(RK_OK);  // the exchange's agreement point
     mr = m;
+    S.last_recv[0] = mr;
   } else {
-    mem = narrow ? (const void *)exchange_nw<uint3>(S, (const uint3 *)mop.out, pp, SL_MEM, &mr)
-                 : (const void *)exchange_nw<uint4>(S, (const uint4 *)mop.out, pp, SL_MEM, &mr);
+    S.plan(mop, m, pp);
+    mop.out = S.take<uint8_t>(SN_SMEM, (pp.total + 1) * (narrow ? 12 : 16));
+    S.emit(mop, pp);
+    mem = narrow ? (const void *)ex((const uint3 *)mop.out, pp, SL_MEM, &mr)
+                 : (const void *)ex((const uint4 *)mop.out, pp, SL_MEM, &mr);
   }
   // the gid range's members: the same 30-bit bound on the member sort
-  if (m_self) S.last_recv[0] = mr;
   S.check_recv_below(1u << 30, RK_E_TOO_MANY, "a gid range of 2^30 or more members");
-  const uint32_t g0 = (uint32_t)gb.b[me], Gl = (uint32_t)(gb.b[me + 1] - gb.b[me]);
-  uint32_t *ogid = S.take<uint32_t>(SL_OGID, mr + 1);
-  uint8_t *orep = S.take<uint8_t>(SL_OREP, mr + 1);
-  uint32_t *oord = S.take<uint32_t>(SL_OORD, mr + 1);
-  if (mr) {
-    const NwDigits ed = nw_plan(bit_length(Gl ? Gl - 1 : 0), narrow ? 9 : 8);
-    uint32_t *sgid = S.take<uint32_t>(SN_SGID, mr + 1);
-    uint32_t *mrow = S.take<uint32_t>(SN_MROW, mr + 1);
-    uint64_t *reckey = S.take<uint64_t>(SN_KEY, mr + 1);
-    uint32_t *tag = S.take<uint32_t>(SN_TAG, mr + 1);
-    uint32_t *otag = S.take<uint32_t>(SL_OTAG, mr + 1);
-    uint32_t *goffs = S.take<uint32_t>(SN_GOFF, (size_t)Gl + 2);
-    uint4 *t0 = S.take<uint4>(SN_T0, mr + 1), *t1 = S.take<uint4>(SN_T1, mr + 1);
-    uint32_t *mstat = S.take<uint32_t>(SN_STAT, nw_status_words(mr + 1));
-    void *gsort = S.take<uint8_t>(SL_GSORT, groupsort_scratch_bytes(mr));
-    S.zero(ehist, 4096 * 4);
-    if (m_self) {
-      nw_rec_hist(gid_own, 4, mr, g0, ed, ehist, st);
-      nw_member_sort(reinterpret_cast<const uint4 *>(erk), gid_own, t0, t1, mr, ed, ehist, mstat,
-                     sgid, reckey, tag, mrow, narrow, st);
-    } else {
-      nw_rec_hist(mem, (int)esz, mr, g0, ed, ehist, st);
-      nw_member_sort_recv(mem, narrow, mr, g0, ed, ehist, mstat, t0, t1, sgid, reckey, tag, mrow,
-                          st);
-    }
-    group_offsets(sgid, mr, Gl, goffs, st);
-    // the group-sort tiers on both streams, as in the single-device path
-    S.check(sort_groups_exact(sgid, goffs, Gl, mr, reckey, tag, otag, gsort,
-                              S.scan_scratch(SL_SCAN, mr + Gl + 2), ctx->host + 128, narrow, st,
-                              st2 != st ? st2 : nullptr, ctx->fork, ctx->join));
-    emit_result(otag, sgid, goffs, mrow, mr, ogid, orep, oord, st);
-    if (g0) k_add_u32<<<grid_for(mr, 256), 256, 0, st>>>(ogid, mr, g0);
-    S.launched("member order");
-  }
+  member_order(S, R, mem, mr, gb, narrow, erk, gid_own, nullptr);
   // every rank's share of the output: its received members
-  std::vector<uint64_t> oall(S.last_recv, S.last_recv + P);
-  uint64_t ooff = 0, otot = 0;
-  for (uint32_t q = 0; q < P; ++q) otot += oall[q], ooff += q < me ? oall[q] : 0;
+  const std::vector<uint64_t> oall(S.last_recv, S.last_recv + P);
   S.hip(hipStreamSynchronize(st), "final sync");
   S.agree_errors();
   ss.ms_members = ms_since(tm);
-
-  out->out_order = oord;
-  out->gid = ogid;
-  out->repval = orep;
-  out->n_out = mr;
-  out->out_offset = ooff;
-  out->n_out_total = otot;
-  out->n_groups = Gtot;
-  (void)N;
-  (void)M;
+  set_result(out, R.oord, R.ogid, R.orep, mr, oall, me, Gtot);
   return RK_OK;
 }

@@ -286,26 +286,37 @@ def test_sharded_edge_fixtures(gpu_ctx, tmp_path):
             assert out.read_bytes() == f.read(), name
 
 
-@pytest.mark.parametrize("env", [None, {"RK_SH_ONE": "0"}, {"RK_SH_YEARLY": "1"}],
-                         ids=["one", "records", "y-early"])
+def _rows(case):  # a SYNTH entry's row count (long_runs.py: 24 buckets of runs_len)
+    return case["n"] if case["kind"] == "synth" else 24 * case["runs_len"]
+
+
+@pytest.mark.parametrize("env", [None, {"RK_SH_ONE": "0"}, {"RK_SH_YEARLY": "1"},
+                                 {"RK_SH_FAST": "0"}],
+                         ids=["one", "records", "y-early", "careful"])
 def test_sharded_world_one(gpu_ctx, tmp_path, env):
     """World size 1: the rows read once as on one device (k_nw_order_hist in
     place of the row checks, the order sort's first pass on the rows; a set
     with a dropped last-bucket row or out-of-bounds rows takes the record
     route), against the single device and the reference's edge fixtures;
     RK_SH_ONE=0 forces the record route, RK_SH_YEARLY=1 the head-first Y
-    schedule."""
+    schedule, RK_SH_FAST=0 the careful driver on the default schedule (its
+    one-rank branches: the identity plans, the members and the rows read in
+    place; on the sets of at most 300,000 rows)."""
+    careful = env == {"RK_SH_FAST": "0"}
+    synth = [c for c in SYNTH if _rows(c) <= 300_000] if careful else SYNTH
     named = _edge_cases()
-    cases = SYNTH + [c for _, c in named]
+    cases = synth + [c for _, c in named]
     got = run_ranks(1, cases, env=env)
-    for ci, case in enumerate(SYNTH):
-        order, gid, rep, ng, _ = assemble(got, ci, 1)
+    for ci, case in enumerate(synth):
+        order, gid, rep, ng, stats = assemble(got, ci, 1)
         want, *_ = reference(gpu_ctx, case)
         assert ng == want.n_groups, case
         assert np.array_equal(order, want.out_order) and np.array_equal(gid, want.gid), case
         assert np.array_equal(rep, want.repval), case
+        if careful:
+            assert all(st["fast_path"] == 0 and st["generic_driver"] == 0 for st in stats), stats
     for cj, (name, case) in enumerate(named):
-        ci = len(SYNTH) + cj
+        ci = len(synth) + cj
         if case["expect"] != "ref":
             kind, code = got[(ci, 0)]
             assert kind == "error" and code == ERR[case["expect"]], (name, kind, code)
