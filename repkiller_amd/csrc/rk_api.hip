@@ -506,7 +506,8 @@ int classify_narrow(rk_ctx *ctx, const rk_frags_soa *in, const rk_params *prms, 
   const rk::NwDigits ad = rk::nw_plan(rk::bit_length(pl.vsize - 1));
   // the processing order in two stages (coarse one-sweep passes + the segment
   // kernel) when the rows are many enough; else LSD passes over every bit
-  const rk::NwOrderPlan op = rk::nw_order_split(n, pl.vsize, rk::bit_length(pl.vsize - 1));
+  const rk::NwOrderPlan op = rk::nw_order_split(n, pl.vsize, rk::bit_length(pl.vsize - 1),
+                                                 rk::NW_SEG_CAP_ORDER);
   const bool split = op.coarse.passes > 0;
   // the widest digit of the 12-B record sorts (Y axis, narrow members): 9
   // bits (7168 records per tile: 14 per digit segment) takes cfg3's 26-bit Y
@@ -529,7 +530,8 @@ int classify_narrow(rk_ctx *ctx, const rk_frags_soa *in, const rk_params *prms, 
   }();
   const rk::NwOrderPlan yp = ysplit_on && !y_overlap
                                  ? rk::nw_order_split(n, 2ull * pl.nby,
-                                                      rk::bit_length(2ull * pl.nby - 1))
+                                                      rk::bit_length(2ull * pl.nby - 1),
+                                                      rk::NW_SEG_CAP_Y)
                                  : rk::NwOrderPlan{};
   const bool ysplit = yp.coarse.passes > 0;
 
@@ -787,7 +789,8 @@ int classify_narrow(rk_ctx *ctx, const rk_frags_soa *in, const rk_params *prms, 
       return e && e[0] == '1';
     }();
     const rk::NwOrderPlan mp = narrow_keys && msplit_on
-                                   ? rk::nw_order_split(m, G, rk::bit_length(G ? G - 1 : 0))
+                                   ? rk::nw_order_split(m, G, rk::bit_length(G ? G - 1 : 0),
+                                                        rk::NW_SEG_CAP_MEMBERS)
                                    : rk::NwOrderPlan{};
     const bool msplit = mp.coarse.passes > 0;
     // (ehist: zero -- cleared at the start, or with the roots' words for q > 0)

@@ -344,8 +344,15 @@ void zero_regions(hipStream_t st, std::initializer_list<ZeroRegion> regs);
 // what nw_order_sort_split_coarse clears first (four regions)
 void nw_order_coarse_regions(uint32_t n, const NwOrderPlan &op, uint32_t *status, uint32_t *chist,
                              ZeroRegion extra, ZeroRegion out[4]);
-NwOrderPlan nw_order_split(uint32_t n, uint64_t nkeys, int bits);  // nkeys: key values in use
-NwOrderPlan nw_order_split_range(uint32_t n, uint64_t klo, uint64_t khi);  // keys in [klo, khi)
+// The segment kernel's LDS capacity (records per block: 8 per thread) of each
+// split sort; a plan aims the average segment at 3/4 of it.  (Measured at
+// cfg3: the Y axis' 12-B records are faster in 256-thread blocks of 2048, the
+// processing order's 16-B records in 512-thread blocks of 4096, DESIGN.md.)
+constexpr uint32_t NW_SEG_CAP_ORDER = 4096, NW_SEG_CAP_Y = 2048, NW_SEG_CAP_MEMBERS = 4096;
+// nkeys: key values in use; cap: the sort's NW_SEG_CAP_*
+NwOrderPlan nw_order_split(uint32_t n, uint64_t nkeys, int bits, uint32_t cap);
+// keys in [klo, khi) (a processing-order sort: NW_SEG_CAP_ORDER)
+NwOrderPlan nw_order_split_range(uint32_t n, uint64_t klo, uint64_t khi);
 // the same in two halves: the clears (+ `extra`) and the coarse passes, then
 // the scan and the segment kernel (cc->cnts cleared by the first half's
 // `extra`) -- the host can read the order histogram's control words back in
@@ -361,7 +368,8 @@ void nw_order_sort_split_fine(uint32_t n, uint32_t m, uint32_t nby, const NwOrde
                               uint32_t *coff, ScanScratch ss, const NwChunkCounts *cc,
                               hipStream_t st);
 // words of each segment array (counts, starts) a split sort of n rows may use
-inline size_t nw_seg_words(uint32_t n) { return (size_t)n / 512 + 64; }
+// (2^C + 1 with 2^C < 4n / (3/4 of the smallest capacity, 2048))
+inline size_t nw_seg_words(uint32_t n) { return (size_t)n / 256 + 64; }
 // the same over records received by the sharded driver (processing index base
 // + position; no X-chunk counts); tmp: m records of scratch
 void nw_order_sort_recs_split(const uint4 *in, uint32_t m, uint32_t nby, uint32_t base,

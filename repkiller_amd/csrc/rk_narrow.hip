@@ -278,11 +278,14 @@ struct DstProc {
   uint32_t base;  // processing index of position 0 (the sharded driver's slice offset)
   __device__ __forceinline__ void store(uint32_t pos, const uint4 &r) const {
     out[pos] = r;
-    const uint64_t ys = rec_y(r);
+    // the centre yc = yStart + length / 2 as bucket yc / 100 and remainder
+    // yc % 100 in 32-bit steps: yStart = hi 2^32 + lo with 2^32 = 42949672 *
+    // 100 + 96, so yc = 100 (hi * 42949672 + lo / 100) + low, low < 2^24
     const uint32_t len = rec_len(r), s = rec_strand(r);
-    const uint64_t yc = ys + len / 2;
-    yrec[pos] = make_uint3(s * nby + (uint32_t)(yc / 100), base + pos,
-                           len | (uint32_t)(yc % 100) << 24);
+    const uint32_t hi = (r.w >> 25) & 7u, ql = r.z / 100u;
+    const uint32_t low = hi * 96u + (r.z - ql * 100u) + len / 2, qs = low / 100u;
+    yrec[pos] = make_uint3(s * nby + (hi * 42949672u + ql + qs), base + pos,
+                           len | (low - qs * 100u) << 24);
   }
 };
 
@@ -455,7 +458,7 @@ struct SrcIdxYX12 {
 // ballots, stable like a record pass -- and writes the final records, the Y
 // records (DstProc's job) and the X-chunk counts (k_nw_xcount's job, which
 // needs the final order).  A segment above the LDS capacity is sorted by the
-// same block through global memory (chunks of OF_CAP in order: stable) --
+// same block through global memory (chunks of the capacity in order: stable) --
 // correct for any input, slow only for pathological ones.
 struct DstRecHist {
   static constexpr bool kWave = true;
@@ -486,7 +489,13 @@ struct DstRec12Hist {
   }
 };
 
-constexpr int OF_T = 512, OF_ITEMS = 8, OF_NW = OF_T / 64, OF_CAP = OF_T * OF_ITEMS;
+// The segment kernels' block shape: T threads hold up to OF_ITEMS records
+// each, so a block's LDS capacity is CAP = T * OF_ITEMS records.
+constexpr int OF_ITEMS = 8;
+template <int T_>
+struct SegShape {
+  static constexpr int T = T_, NW = T_ / 64, CAP = T_ * OF_ITEMS;
+};
 // the records inside the segment kernels as plain structs (kept in HIP's
 // vector types, the 16-B records' y/z/w went through a scratch array)
 struct P4 {
@@ -509,26 +518,34 @@ struct PodOf<uint3> {
   __device__ static __forceinline__ P3 from(const uint3 &v) { return P3{v.x, v.y, v.z}; }
   __device__ static __forceinline__ uint3 to(const P3 &v) { return make_uint3(v.x, v.y, v.z); }
 };
-template <class R>
+template <class R, class S>
 struct FineLds {
-  typename PodOf<R>::type srec[OF_CAP];
-  uint32_t wcnt[OF_NW][256];  // per-wave digit counters, then per-wave starts
+  typename PodOf<R>::type srec[S::CAP];
+  uint32_t wcnt[S::NW][256];  // per-wave digit counters, then per-wave starts
   uint32_t lbase[256];        // block-local digit starts
-  uint32_t run[256];          // global path: running digit offsets
-  uint32_t tot[256];          // global path: digit totals of a chunk / histogram
-  uint32_t wsum[OF_NW];
+  uint32_t wsum[S::NW];
+};
+// what only the global-memory path (k_seg_big) keeps beside it
+struct BigLds {
+  uint32_t run[256];  // running digit offsets
+  uint32_t tot[256];  // digit totals of a chunk / histogram
 };
 
 // Stable ranks of the block's records by digit d = (x >> shift) & (2^db - 1)
-// (x = the record's fine key): rec[r] sits at block index wbase + 64 r, live
-// below cnt.  Returns in rk[r] the record's slot among the wave's records of
-// its digit; afterwards L.wcnt[w][d] = wave w's start inside digit d, L.lbase[d]
-// = digit d's start in the block, L.tot[d] = its count.
-template <class R, class V>
-__device__ __forceinline__ void fine_rank(FineLds<R> &L, const V (&rec)[OF_ITEMS],
-                                          uint32_t (&rk)[OF_ITEMS], uint32_t (&dg)[OF_ITEMS],
-                                          uint32_t wbase, uint32_t cnt, uint32_t fmask, int shift,
-                                          int db) {
+// (x = the record's fine key).  The block's cnt records are split evenly and
+// in order: nit = ceil(cnt / T) items per lane (block-uniform, 1..OF_ITEMS),
+// wave w holding the indices [64 nit w, 64 nit (w + 1)), its rec[r] (r < nit)
+// at index wbase + 64 r with wbase = 64 nit w + lane, live below cnt; items
+// r >= nit are skipped.  Returns in rk[r] the record's slot among the wave's
+// records of its digit (low 16 bits) with the digit above it (one register
+// per record: kept apart, the order kernel's records spilled); afterwards
+// L.wcnt[w][d] = wave w's start inside digit d, L.lbase[d] = digit d's start
+// in the block, totp[d] (when given: the global-memory path) = its count.
+template <class R, class S, class V>
+__device__ __forceinline__ void fine_rank(FineLds<R, S> &L, const V (&rec)[OF_ITEMS],
+                                          uint32_t (&rk)[OF_ITEMS], uint32_t wbase, int nit,
+                                          uint32_t cnt, uint32_t fmask, int shift, int db,
+                                          uint32_t *totp) {
   const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const uint64_t lt = (1ull << lane) - 1ull;
   uint32_t *mycnt = L.wcnt[w];
@@ -537,21 +554,22 @@ __device__ __forceinline__ void fine_rank(FineLds<R> &L, const V (&rec)[OF_ITEMS
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 #pragma unroll
   for (int r = 0; r < OF_ITEMS; ++r) {
-    const bool live = wbase + 64 * r < cnt;
-    const uint32_t d = live ? ((rec[r].x & fmask) >> shift) & ((1u << db) - 1u) : 0u;
-    dg[r] = d;
-    uint64_t peer = __ballot(live);
-    for (int b = 0; b < db; ++b) {
-      const bool bit = (d >> b) & 1u;
-      const uint64_t bb = __ballot(bit);
-      peer &= bit ? bb : ~bb;
+    if (r < nit) {
+      const bool live = wbase + 64 * r < cnt;
+      const uint32_t d = live ? ((rec[r].x & fmask) >> shift) & ((1u << db) - 1u) : 0u;
+      uint64_t peer = __ballot(live);
+      for (int b = 0; b < db; ++b) {
+        const bool bit = (d >> b) & 1u;
+        const uint64_t bb = __ballot(bit);
+        peer &= bit ? bb : ~bb;
+      }
+      const uint32_t below = __popcll(peer & lt);
+      const uint32_t before = live ? mycnt[d] : 0u;
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      if (live && below == 0) mycnt[d] = before + __popcll(peer);
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      rk[r] = (before + below) | (d << 16);
     }
-    const uint32_t below = __popcll(peer & lt);
-    const uint32_t before = live ? mycnt[d] : 0u;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    if (live && below == 0) mycnt[d] = before + __popcll(peer);
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    rk[r] = before + below;
   }
   __syncthreads();
   // thread t < 256 owns digit t: the waves' starts inside it, then the block scan
@@ -559,7 +577,7 @@ __device__ __forceinline__ void fine_rank(FineLds<R> &L, const V (&rec)[OF_ITEMS
   uint32_t tot = 0;
   if (t < 256) {
 #pragma unroll
-    for (int k = 0; k < OF_NW; ++k) {
+    for (int k = 0; k < S::NW; ++k) {
       const uint32_t c = L.wcnt[k][t];
       L.wcnt[k][t] = tot;
       tot += c;
@@ -576,7 +594,7 @@ __device__ __forceinline__ void fine_rank(FineLds<R> &L, const V (&rec)[OF_ITEMS
     uint32_t at = inc - tot;
     for (uint32_t k = 0; k < w; ++k) at += L.wsum[k];
     L.lbase[t] = at;
-    L.tot[t] = tot;
+    if (totp) totp[t] = tot;
   }
   __syncthreads();
 }
@@ -596,7 +614,7 @@ struct OrderEmit {
   DstProc dst;
   uint32_t m;      // kept rows: the X counts take positions below m
   uint32_t *cnts;  // X-chunk counts, or null
-  uint32_t lgW, nch, kdiv;
+  uint32_t lgW, nch, kdiv;  // (kdiv = 10 << lgW: the chunk width is a power of two)
   // the window's first chunk, after clearing the window
   __device__ __forceinline__ uint32_t begin(uint32_t *win, uint32_t key0) const {
     for (uint32_t j = threadIdx.x; j < (uint32_t)kWin; j += blockDim.x) win[j] = 0;
@@ -610,8 +628,11 @@ struct OrderEmit {
       const bool kept = live && pos < m;
       uint32_t vx = NONE, vo = NONE;
       if (kept) {
-        const uint32_t cx = (uint32_t)((rec_x(r) + rec_len(r) / 2) / 100) >> lgW;
-        const uint32_t co = r.x / kdiv, st = rec_strand(r);
+        // (xStart + length / 2) / 100 and key / kdiv in 32-bit steps: xStart =
+        // 100 (key / 10) + 10 (key % 10) + its last digit, kdiv = 10 << lgW
+        const uint32_t q = r.x / 10u, low = (r.x - q * 10u) * 10u + (r.w >> 28) + rec_len(r) / 2;
+        const uint32_t cx = (q + low / 100u) >> lgW;
+        const uint32_t co = (r.x >> lgW) / 10u, st = rec_strand(r);
         if (cx - w0 < OE_WIN) vx = st * OE_WIN + (cx - w0);
         else atomicAdd(&cnts[st * nch + cx], 1u);
         if (co - w0 < OE_WIN) vo = 2 * OE_WIN + (co - w0);
@@ -669,9 +690,10 @@ struct CsrEmit {
 };
 
 // One block per segment: the F fine bits of its records, LSD by digits of up
-// to 8 bits, in LDS (at most OF_CAP records).  A larger segment is listed in
-// big (big[0] = count) for k_seg_big: kept apart, the LDS kernel's registers
-// hold no global-memory path (with it inline the records spilled to scratch).
+// to 8 bits, in LDS (at most S::CAP records), the records split evenly over
+// the block's waves (fine_rank).  A larger segment is listed in big (big[0] =
+// count) for k_seg_big: kept apart, the LDS kernel's registers hold no
+// global-memory path (with it inline the records spilled to scratch).
 template <class R>
 struct SegArgs {
   const R *in;          // sorted by coarse key, stable
@@ -679,51 +701,58 @@ struct SegArgs {
   const uint32_t *off;  // nseg + 1 segment starts
   uint32_t nseg;
   int F;                // fine bits (>= 1)
-  uint32_t *big;        // [0] count, then the segments above OF_CAP
+  uint32_t *big;        // [0] count, then the segments above the kernel's capacity
 };
-template <class R, class E>
-__global__ void __launch_bounds__(OF_T) __attribute__((amdgpu_waves_per_eu(4)))
+template <class R, class E, class S>
+__global__ void __launch_bounds__(S::T) __attribute__((amdgpu_waves_per_eu(4)))
 k_seg_fine(const SegArgs<R> a, const E e) {
-  __shared__ FineLds<R> L;
+  __shared__ FineLds<R, S> L;
   __shared__ uint32_t ewin[E::kWin];
   const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6, t = threadIdx.x;
-  const uint32_t wbase = w * (OF_CAP / OF_NW) + lane;
   const uint32_t fmask = a.F >= 32 ? 0xFFFFFFFFu : (1u << a.F) - 1u;
   const int np = (a.F + 7) / 8;
   using P = PodOf<R>;
   typename P::type rec[OF_ITEMS];
-  uint32_t rk[OF_ITEMS], dg[OF_ITEMS];
+  uint32_t rk[OF_ITEMS];
   for (uint32_t sg = blockIdx.x; sg < a.nseg; sg += gridDim.x) {
     const uint32_t s0 = a.off[sg], cnt = a.off[sg + 1] - s0;
     if (cnt == 0) continue;
-    if (cnt > (uint32_t)OF_CAP) {
+    if (cnt > (uint32_t)S::CAP) {
       if (t == 0) a.big[1 + atomicAdd(&a.big[0], 1u)] = sg;
       continue;
     }
+    // (block-uniform: the item loops below branch on it without divergence)
+    const int nit = __builtin_amdgcn_readfirstlane((int)((cnt + S::T - 1) / S::T));
+    const uint32_t wbase = 64u * nit * w + lane;
+    // (every item, the dead ones a copy of the last record: behind a branch on
+    // nit each load waited for its data before the next one issued)
 #pragma unroll
     for (int r = 0; r < OF_ITEMS; ++r) {
       const uint32_t i = wbase + 64 * r;
-      rec[r] = P::from(a.in[s0 + (i < cnt ? i : cnt - 1)]);  // (dead lanes: a copy, no branch)
+      rec[r] = P::from(a.in[s0 + (i < cnt ? i : cnt - 1)]);
     }
     // LSD passes over the fine key; the last placement is the final order
     for (int q = 0; q < np; ++q) {
       const int shift = 8 * q, db = a.F - shift < 8 ? a.F - shift : 8;
-      fine_rank(L, rec, rk, dg, wbase, cnt, fmask, shift, db);
+      fine_rank(L, rec, rk, wbase, nit, cnt, fmask, shift, db, nullptr);
 #pragma unroll
       for (int r = 0; r < OF_ITEMS; ++r)
-        if (wbase + 64 * r < cnt) L.srec[L.lbase[dg[r]] + L.wcnt[w][dg[r]] + rk[r]] = rec[r];
+        if (r < nit && wbase + 64 * r < cnt) {
+          const uint32_t d = rk[r] >> 16;
+          L.srec[L.lbase[d] + L.wcnt[w][d] + (rk[r] & 0xFFFFu)] = rec[r];
+        }
       __syncthreads();
       if (q + 1 < np) {
 #pragma unroll
         for (int r = 0; r < OF_ITEMS; ++r) {
           const uint32_t i = wbase + 64 * r;
-          rec[r] = L.srec[i < cnt ? i : cnt - 1];  // (unconditional: the array stays in VGPRs)
+          rec[r] = L.srec[i < cnt ? i : cnt - 1];  // (no branch: the reads issue together)
         }
         __syncthreads();
       }
     }
     const uint32_t w0 = e.begin(ewin, L.srec[0].x);
-    for (uint32_t j0 = 0; j0 < cnt; j0 += OF_T) {
+    for (uint32_t j0 = 0; j0 < cnt; j0 += S::T) {
       const uint32_t j = j0 + t;
       const bool live = j < cnt;
       const R r = P::to(L.srec[live ? j : cnt - 1]);
@@ -735,50 +764,50 @@ k_seg_fine(const SegArgs<R> a, const E e) {
   }
 }
 
-// The listed segments above OF_CAP, one block each: the same passes through
+// The listed segments above S::CAP, one block each: the same passes through
 // global memory, chunk by chunk in order (stable); the last lands in A.  A
 // segment whose fine keys are all equal (one huge group of the member sort)
 // is already in order.
-template <class R, class E>
-__global__ void __launch_bounds__(OF_T) k_seg_big(const SegArgs<R> a, const E e) {
-  __shared__ FineLds<R> L;
+template <class R, class E, class S>
+__global__ void __launch_bounds__(S::T) k_seg_big(const SegArgs<R> a, const E e) {
+  __shared__ FineLds<R, S> L;
+  __shared__ BigLds G;
   __shared__ uint32_t ewin[E::kWin];
   const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6, t = threadIdx.x;
-  const uint32_t wbase = w * (OF_CAP / OF_NW) + lane;
   const uint32_t fmask = a.F >= 32 ? 0xFFFFFFFFu : (1u << a.F) - 1u;
   const int np = (a.F + 7) / 8;
   using P = PodOf<R>;
   typename P::type rec[OF_ITEMS];
-  uint32_t rk[OF_ITEMS], dg[OF_ITEMS];
+  uint32_t rk[OF_ITEMS];
   const uint32_t nbig = a.big[0];
   for (uint32_t k = blockIdx.x; k < nbig; k += gridDim.x) {
     const uint32_t sg = a.big[1 + k];
     const uint32_t s0 = a.off[sg], cnt = a.off[sg + 1] - s0;
     const R *src = a.in + s0;
     uint32_t lo = 0xFFFFFFFFu, hi = 0;
-    for (uint32_t j = t; j < cnt; j += OF_T) {
+    for (uint32_t j = t; j < cnt; j += S::T) {
       const uint32_t x = src[j].x & fmask;
       lo = x < lo ? x : lo;
       hi = x > hi ? x : hi;
     }
-    if (t == 0) L.run[0] = 0xFFFFFFFFu, L.run[1] = 0;
+    if (t == 0) G.run[0] = 0xFFFFFFFFu, G.run[1] = 0;
     __syncthreads();
-    atomicMin(&L.run[0], lo);
-    atomicMax(&L.run[1], hi);
+    atomicMin(&G.run[0], lo);
+    atomicMax(&G.run[1], hi);
     __syncthreads();
-    const bool sorted = L.run[0] == L.run[1];
+    const bool sorted = G.run[0] == G.run[1];
     __syncthreads();
     for (int q = 0; q < (sorted ? 0 : np); ++q) {
       const int shift = 8 * q, db = a.F - shift < 8 ? a.F - shift : 8;
       R *dst = ((np - 1 - q) % 2 == 0) ? a.A + s0 : a.B + s0;
       // the pass' digit histogram over the segment, its scan into running starts
-      if (t < 256) L.tot[t] = 0;
+      if (t < 256) G.tot[t] = 0;
       __syncthreads();
-      for (uint32_t j = t; j < cnt; j += OF_T)
-        atomicAdd(&L.tot[((src[j].x & fmask) >> shift) & ((1u << db) - 1u)], 1u);
+      for (uint32_t j = t; j < cnt; j += S::T)
+        atomicAdd(&G.tot[((src[j].x & fmask) >> shift) & ((1u << db) - 1u)], 1u);
       __syncthreads();
       {
-        const uint32_t tot = t < 256 ? L.tot[t] : 0u;
+        const uint32_t tot = t < 256 ? G.tot[t] : 0u;
         uint32_t inc = tot;
         for (int o = 1; o < 64; o <<= 1) {
           const uint32_t v = __shfl_up(inc, o);
@@ -789,23 +818,29 @@ __global__ void __launch_bounds__(OF_T) k_seg_big(const SegArgs<R> a, const E e)
         if (t < 256) {
           uint32_t at = inc - tot;
           for (uint32_t k2 = 0; k2 < w; ++k2) at += L.wsum[k2];
-          L.run[t] = at;
+          G.run[t] = at;
         }
         __syncthreads();
       }
-      for (uint32_t c0 = 0; c0 < cnt; c0 += OF_CAP) {
-        const uint32_t cc = cnt - c0 < (uint32_t)OF_CAP ? cnt - c0 : (uint32_t)OF_CAP;
+      for (uint32_t c0 = 0; c0 < cnt; c0 += S::CAP) {
+        const uint32_t cc = cnt - c0 < (uint32_t)S::CAP ? cnt - c0 : (uint32_t)S::CAP;
+        // (a full chunk: OF_ITEMS items per lane; the last one split evenly)
+        const int nit = __builtin_amdgcn_readfirstlane((int)((cc + S::T - 1) / S::T));
+        const uint32_t wbase = 64u * nit * w + lane;
 #pragma unroll
         for (int r = 0; r < OF_ITEMS; ++r) {
           const uint32_t i = wbase + 64 * r;
           rec[r] = P::from(src[c0 + (i < cc ? i : cc - 1)]);
         }
-        fine_rank(L, rec, rk, dg, wbase, cc, fmask, shift, db);
+        fine_rank(L, rec, rk, wbase, nit, cc, fmask, shift, db, G.tot);
 #pragma unroll
         for (int r = 0; r < OF_ITEMS; ++r)
-          if (wbase + 64 * r < cc) dst[L.run[dg[r]] + L.wcnt[w][dg[r]] + rk[r]] = P::to(rec[r]);
+          if (r < nit && wbase + 64 * r < cc) {
+            const uint32_t d = rk[r] >> 16;
+            dst[G.run[d] + L.wcnt[w][d] + (rk[r] & 0xFFFFu)] = P::to(rec[r]);
+          }
         __syncthreads();
-        if (t < 256) L.run[t] += L.tot[t];
+        if (t < 256) G.run[t] += G.tot[t];
         __syncthreads();
       }
       // this block's global writes before its next reads of them: one CU,
@@ -816,7 +851,7 @@ __global__ void __launch_bounds__(OF_T) k_seg_big(const SegArgs<R> a, const E e)
     }
     const R *fin = sorted ? a.in + s0 : a.A + s0;
     const uint32_t w0 = e.begin(ewin, fin[0].x);
-    for (uint32_t j0 = 0; j0 < cnt; j0 += OF_T) {
+    for (uint32_t j0 = 0; j0 < cnt; j0 += S::T) {
       const uint32_t j = j0 + t;
       const bool live = j < cnt;
       const R r = fin[live ? j : cnt - 1];
@@ -828,12 +863,12 @@ __global__ void __launch_bounds__(OF_T) k_seg_big(const SegArgs<R> a, const E e)
   }
 }
 
-template <class R, class E>
+template <class S, class R, class E>
 static void launch_seg(const SegArgs<R> &a, const E &e, hipStream_t st) {
   // (a.big[0], the list count, is the segment counts' first word: the scan
   // that placed the segments cleared it, exclusive_scan_u32_clear0)
-  k_seg_fine<<<a.nseg < 65536u ? a.nseg : 65536u, OF_T, 0, st>>>(a, e);
-  k_seg_big<<<256, OF_T, 0, st>>>(a, e);  // (returns at once when none is listed)
+  k_seg_fine<R, E, S><<<a.nseg < 65536u ? a.nseg : 65536u, S::T, 0, st>>>(a, e);
+  k_seg_big<R, E, S><<<256, S::T, 0, st>>>(a, e);  // (returns at once when none is listed)
 }
 
 // --- group members, last pass: gid order (stable: processing order inside) -
@@ -1689,13 +1724,16 @@ void nw_order_sort_recs(const uint4 *in, uint32_t m, uint32_t nby, uint32_t base
 
 // The two-stage plan (see k_seg_fine): F fine bits for the segment
 // kernel -- as many as keep the average segment (n rows over the nkeys key
-// values, 2^F keys per segment) at most NW_SEG_TARGET rows, 3/4 of the LDS
-// capacity (cfg3: ~2730 rows; the global-memory path stays rare) -- and
+// values, 2^F keys per segment) at most 3/4 of the segment kernel's LDS
+// capacity `cap` (NW_SEG_CAP_*; the global-memory path stays rare) -- and
 // C = b - F coarse bits for the one-sweep passes.  passes = 0: the LSD passes
 // over all b bits (too few rows, or RK_NW_SPLIT=0).
-constexpr uint32_t NW_SEG_TARGET = OF_CAP * 3 / 4;
-NwOrderPlan nw_order_split(uint32_t n, uint64_t nkeys, int b) {
+using ShapeOrder = SegShape<NW_SEG_CAP_ORDER / OF_ITEMS>;
+using ShapeY = SegShape<NW_SEG_CAP_Y / OF_ITEMS>;
+using ShapeMembers = SegShape<NW_SEG_CAP_MEMBERS / OF_ITEMS>;
+NwOrderPlan nw_order_split(uint32_t n, uint64_t nkeys, int b, uint32_t cap) {
   NwOrderPlan o{};
+  const uint32_t NW_SEG_TARGET = cap * 3 / 4;
   static const bool on = [] {
     const char *e = getenv("RK_NW_SPLIT");
     return !(e && e[0] == '0');
@@ -1718,13 +1756,14 @@ NwOrderPlan nw_order_split(uint32_t n, uint64_t nkeys, int b) {
 // bits stay the key's own low F bits
 NwOrderPlan nw_order_split_range(uint32_t n, uint64_t klo, uint64_t khi) {
   if (khi <= klo) return NwOrderPlan{};
+  constexpr uint32_t NW_SEG_TARGET = NW_SEG_CAP_ORDER * 3 / 4;
   // F as nw_order_split picks it (capped by the absolute key's bits)
   const int b = bit_length(khi - 1);
   int F = 0;
   while (F < b && (double)n * (double)(2ull << F) <= (double)NW_SEG_TARGET * (double)(khi - klo))
     ++F;
   const uint64_t kbase = klo & ~((1ull << F) - 1);
-  NwOrderPlan o = nw_order_split(n, khi - klo, bit_length(khi - 1 - kbase));
+  NwOrderPlan o = nw_order_split(n, khi - klo, bit_length(khi - 1 - kbase), NW_SEG_CAP_ORDER);
   // (its F is at most this F -- the same density test, a smaller cap -- so
   // kbase stays a multiple of 2^o.F)
   if (o.nseg && (kbase & ((1ull << o.F) - 1))) return NwOrderPlan{};
@@ -1796,8 +1835,8 @@ static void nw_order_fine(uint32_t n, uint32_t m, uint32_t nby, uint32_t base,
     oe.kdiv = 10 * cc->W;
   }
   kt_begin(st, KID_NW_FINE);
-  // (the counts are free after the scan: the list of segments above OF_CAP)
-  launch_seg(SegArgs<uint4>{Rb, Ra, tmp, coff, op.nseg, op.F, chist}, oe, st);
+  // (the counts are free after the scan: the list of segments above the capacity)
+  launch_seg<ShapeOrder>(SegArgs<uint4>{Rb, Ra, tmp, coff, op.nseg, op.F, chist}, oe, st);
   // records in and out, Y records out (the X counts: no extra reads)
   kt_end(st, KID_NW_FINE, 44.0 * n);
 }
@@ -1993,8 +2032,8 @@ void nw_y_sort_split_after_x(uint4 *yrec, uint4 *tmp, uint4 *tmp2, uint32_t m,
   exclusive_scan_u32_clear0(chist, coff, (size_t)yp.nseg + 1, ss, st);
   const DstCsr dc{cy.key, cy.ent, cy.pk, cy.nbd, nby, max_y, nullptr, cy.state, true};
   kt_begin(st, KID_NW_YFINE);
-  // (the counts are free after the scan: the list of segments above OF_CAP)
-  launch_seg(SegArgs<uint3>{a, reinterpret_cast<uint3 *>(yrec), b, coff, yp.nseg, yp.F, chist},
+  // (the counts are free after the scan: the list of segments above the capacity)
+  launch_seg<ShapeY>(SegArgs<uint3>{a, reinterpret_cast<uint3 *>(yrec), b, coff, yp.nseg, yp.F, chist},
              CsrEmit{dc}, st);
   // records in; key, entry, packed record, neighbour code and state out
   kt_end(st, KID_NW_YFINE, 30.0 * m);
@@ -2081,7 +2120,7 @@ void nw_member_sort_split(const uint4 *erec, const uint32_t *gidp, uint4 *t0, ui
   }
   exclusive_scan_u32_clear0(chist, coff, (size_t)mp.nseg + 1, ss, st);
   kt_begin(st, KID_NW_MFINE);
-  launch_seg(SegArgs<uint3>{b, a, c, coff, mp.nseg, mp.F, chist},
+  launch_seg<ShapeMembers>(SegArgs<uint3>{b, a, c, coff, mp.nseg, mp.F, chist},
              MemberEmit{sgid, tag, mrow, key, goff, G, m}, st);
   // records in; gid, row, key (8 B), tag out; the group starts
   kt_end(st, KID_NW_MFINE, 32.0 * m + 4.0 * G);
