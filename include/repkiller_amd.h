@@ -142,6 +142,59 @@ int rk_get_stats(const rk_ctx *ctx, rk_stats *st);
 enum { RK_PIPELINE_AUTO = 0, RK_PIPELINE_GENERIC = 1 };
 int rk_set_pipeline(rk_ctx *ctx, int pipeline);
 
+/* ---- MANY fragment sets in one call ------------------------------------
+ *
+ * An all-against-all comparison leaves hundreds of fragment CSVs of a few
+ * thousand rows each; classified one per call, each pays the pipeline's fixed
+ * cost (its launches and host round trips).  rk_classify_batch classifies
+ * them together: every set is translated into its own window of one combined
+ * coordinate space (rk_batch_layout), the combined set runs through the record
+ * pipeline once, and the result is split back (DESIGN.md "Batched sets").
+ * For every set the five outputs are byte-identical to what rk_classify /
+ * rk_classify_device returns for that set alone with the same ratios.
+ */
+typedef struct {
+  uint32_t nsets;
+  const uint64_t *set_off;   /* HOST, nsets + 1 entries, non-decreasing: set k is rows
+                                [set_off[k], set_off[k+1]) of `in` */
+  const uint64_t *len_x_hdr; /* HOST, per set: raw header values, as rk_params */
+  const uint64_t *len_y_hdr;
+  double len_ratio, pos_ratio; /* one pair for the whole batch */
+} rk_batch_params;
+
+typedef struct {
+  /* caller-allocated, set_off[nsets] entries each; set k's result occupies
+   * [set_off[k], set_off[k] + n_out[k]) exactly as rk_classify would fill a
+   * result for that set alone: out_order and gid are LOCAL to the set */
+  uint32_t *out_order, *gid;
+  uint8_t *repval;
+  uint64_t *n_out, *n_groups; /* HOST, nsets entries */
+} rk_batch_result;
+
+/* `in`: the concatenation of all sets in file order.  If a set would fail on
+ * its own, the call returns that status for the lowest-numbered such set
+ * (rk_last_error names it, "set K") and promises nothing else about the
+ * outputs.  RK_E_ARG: a ratio <= 0, null arrays with rows present, a
+ * decreasing set_off.  nsets == 0 is RK_OK. */
+int rk_classify_batch(rk_ctx *ctx, const rk_frags_soa *in, const rk_batch_params *p,
+                      rk_batch_result *out); /* host rows / results */
+int rk_classify_device_batch(rk_ctx *ctx, const rk_frags_soa *in_dev, const rk_batch_params *p,
+                             rk_batch_result *out); /* device rows / results */
+/* The windows: set k's rows are translated by base_x[k] / base_y[k] (multiples
+ * of 100; base[0] = 0; nsets + 1 entries each, the last the combined extent).
+ * Pure host arithmetic, no device.  RK_E_ARG when the extent overflows. */
+int rk_batch_layout(uint32_t nsets, const uint64_t *len_x_hdr, const uint64_t *len_y_hdr,
+                    uint64_t *base_x, uint64_t *base_y);
+/* The last rk_classify*_batch call on a context: combined classifications
+ * run, sets classified one by one through the single-set path (a sub-batch
+ * the record pipeline cannot take, or a set that fits no sub-batch), sets
+ * classified combined, and the device time of all of it. */
+typedef struct {
+  uint32_t sub_batches, looped_sets, batched_sets;
+  double device_ms;
+} rk_batch_stats;
+int rk_get_batch_stats(const rk_ctx *ctx, rk_batch_stats *st);
+
 /* ---- ONE fragment set sharded over several GPUs ----------------------
  *
  * The reference runs the whole path on one host thread per ratio pair

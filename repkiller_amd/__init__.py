@@ -51,6 +51,7 @@ EXPORTS = (
     "rk_comm_destroy", "rk_comm_last_error", "rk_classify_sharded", "rk_get_shard_stats",
     "rk_shard_copy_result", "rk_comm_create_local", "rk_classify_sharded_host",
     "rk_comm_abandon", "rk_set_pipeline",
+    "rk_classify_batch", "rk_classify_device_batch", "rk_batch_layout", "rk_get_batch_stats",
 )
 
 
@@ -92,6 +93,23 @@ class Stats(ctypes.Structure):
                 ("sweep_repeats", ctypes.c_uint32), ("numa_input", ctypes.c_int32),
                 ("numa_threads", ctypes.c_int32), ("numa_staging", ctypes.c_int32),
                 ("numa_gpu", ctypes.c_int32)]
+
+
+class BatchParams(ctypes.Structure):
+    _fields_ = [("nsets", ctypes.c_uint32), ("set_off", ctypes.c_void_p),
+                ("len_x_hdr", ctypes.c_void_p), ("len_y_hdr", ctypes.c_void_p),
+                ("len_ratio", ctypes.c_double), ("pos_ratio", ctypes.c_double)]
+
+
+class BatchResult(ctypes.Structure):
+    _fields_ = [("out_order", ctypes.c_void_p), ("gid", ctypes.c_void_p),
+                ("repval", ctypes.c_void_p), ("n_out", ctypes.c_void_p),
+                ("n_groups", ctypes.c_void_p)]
+
+
+class BatchStats(ctypes.Structure):
+    _fields_ = [("sub_batches", ctypes.c_uint32), ("looped_sets", ctypes.c_uint32),
+                ("batched_sets", ctypes.c_uint32), ("device_ms", ctypes.c_double)]
 
 
 ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
@@ -211,6 +229,14 @@ def load_library() -> ctypes.CDLL:
                                                     ctypes.POINTER(Params), ctypes.c_int32,
                                                     ctypes.POINTER(ShardResult)]),
         "rk_shard_copy_result": (ctypes.c_int, [vp, ctypes.POINTER(ShardResult), vp, vp, vp]),
+        "rk_classify_batch": (ctypes.c_int, [vp, ctypes.POINTER(FragsSoA),
+                                             ctypes.POINTER(BatchParams),
+                                             ctypes.POINTER(BatchResult)]),
+        "rk_classify_device_batch": (ctypes.c_int, [vp, ctypes.POINTER(FragsSoA),
+                                                    ctypes.POINTER(BatchParams),
+                                                    ctypes.POINTER(BatchResult)]),
+        "rk_batch_layout": (ctypes.c_int, [ctypes.c_uint32, vp, vp, vp, vp]),
+        "rk_get_batch_stats": (ctypes.c_int, [vp, ctypes.POINTER(BatchStats)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -543,6 +569,86 @@ class Context:
         if rc != RK_OK:
             raise RkError(rc, self.last_error())
         return int(res.n_out), int(res.n_groups)
+
+
+    def classify_batch(self, sets, len_ratio: float = 0.3, pos_ratio: float = 0.3,
+                       set_off=None) -> list:
+        """Many fragment sets in one call (rk_classify_batch).  ``sets``: a list of
+        ``(Frags, len_x_hdr, len_y_hdr)``; returns one :class:`ClassifyResult` per
+        set, each what :meth:`classify` returns for that set alone.  ``set_off``
+        (tests): the row offsets handed to the library instead of the sets' own."""
+        sets = list(sets)
+        ns = len(sets)
+        cols = []
+        for name, t in (("x_start", np.uint64), ("y_start", np.uint64), ("length", np.uint64),
+                        ("strand", np.uint8)):
+            parts = [np.ascontiguousarray(getattr(f, name), dtype=t) for f, _, _ in sets]
+            cols.append(np.concatenate(parts) if parts else np.empty(0, t))
+        off = np.zeros(ns + 1, np.uint64)
+        if ns:
+            off[1:] = np.cumsum([f.n for f, _, _ in sets], dtype=np.uint64)
+        if set_off is not None:
+            off = np.ascontiguousarray(set_off, np.uint64)
+        n = int(cols[0].shape[0])
+        lx = np.array([s[1] for s in sets], np.uint64)
+        ly = np.array([s[2] for s in sets], np.uint64)
+        gid, rep, order = np.zeros(n, np.uint32), np.zeros(n, np.uint8), np.zeros(n, np.uint32)
+        n_out, n_groups = np.zeros(ns, np.uint64), np.zeros(ns, np.uint64)
+        soa = FragsSoA(_ptr(cols[0]), _ptr(cols[1]), _ptr(cols[2]), _ptr(cols[3]), n)
+        prm = BatchParams(ns, off.ctypes.data, _ptr(lx), _ptr(ly), len_ratio, pos_ratio)
+        res = BatchResult(_ptr(order), _ptr(gid), _ptr(rep), _ptr(n_out), _ptr(n_groups))
+        rc = load_library().rk_classify_batch(self._h, ctypes.byref(soa), ctypes.byref(prm),
+                                              ctypes.byref(res))
+        if rc != RK_OK:
+            raise RkError(rc, self.last_error())
+        out = []
+        for k in range(ns):
+            a = int(off[k])
+            b = a + int(n_out[k])
+            out.append(ClassifyResult(gid[a:b].copy(), rep[a:b].copy(), order[a:b].copy(),
+                                      int(n_groups[k])))
+        return out
+
+    def classify_device_batch(self, x, y, length, strand, gid, repval, out_order, set_off,
+                              len_x_hdr, len_y_hdr, len_ratio: float = 0.3,
+                              pos_ratio: float = 0.3):
+        """Device tensors in and out (rk_classify_device_batch): the concatenated
+        rows of all sets, ``set_off`` / ``len_x_hdr`` / ``len_y_hdr`` host sequences.
+        Set k's result is entries [set_off[k], set_off[k] + n_out[k]) of the output
+        tensors.  Returns (n_out, n_groups) as uint64 arrays."""
+        off = np.ascontiguousarray(set_off, np.uint64)
+        ns = off.shape[0] - 1
+        lx = np.ascontiguousarray(len_x_hdr, np.uint64)
+        ly = np.ascontiguousarray(len_y_hdr, np.uint64)
+        n_out, n_groups = np.zeros(ns, np.uint64), np.zeros(ns, np.uint64)
+        soa = FragsSoA(x.data_ptr(), y.data_ptr(), length.data_ptr(), strand.data_ptr(),
+                       int(x.shape[0]))
+        prm = BatchParams(ns, off.ctypes.data, _ptr(lx), _ptr(ly), len_ratio, pos_ratio)
+        res = BatchResult(out_order.data_ptr(), gid.data_ptr(), repval.data_ptr(), _ptr(n_out),
+                          _ptr(n_groups))
+        rc = load_library().rk_classify_device_batch(self._h, ctypes.byref(soa),
+                                                     ctypes.byref(prm), ctypes.byref(res))
+        if rc != RK_OK:
+            raise RkError(rc, self.last_error())
+        return n_out, n_groups
+
+    def batch_stats(self) -> dict:
+        """Counters of the last classify*_batch call (rk_get_batch_stats)."""
+        s = BatchStats()
+        _check(load_library().rk_get_batch_stats(self._h, ctypes.byref(s)))
+        return {k: getattr(s, k) for k, _ in BatchStats._fields_}
+
+
+def batch_layout(len_x, len_y):
+    """The windows of a batch (rk_batch_layout): (base_x, base_y), nsets + 1
+    entries each, in coordinates; set k's rows are translated by base[k]."""
+    lx = np.ascontiguousarray(len_x, np.uint64)
+    ly = np.ascontiguousarray(len_y, np.uint64)
+    ns = lx.shape[0]
+    bx, by = np.zeros(ns + 1, np.uint64), np.zeros(ns + 1, np.uint64)
+    _check(load_library().rk_batch_layout(ns, _ptr(lx), _ptr(ly), bx.ctypes.data, by.ctypes.data),
+           "rk_batch_layout")
+    return bx, by
 
 
 # ---------------------------------------------------- one set over many GPUs --

@@ -637,6 +637,8 @@ int classify_narrow(rk_ctx *ctx, const rk_frags_soa *in, const rk_params *prms, 
   mark(ctx, RK_PH_GATHER);
   rk::nw_x_chunks(w.Ra, m, pl.nbx, pl.max_x, maxlen, w.xoff, w.cx, w.xpos, w.erec, w.ctrl, cc.W,
                   st);
+  // a batch's combined set: the upward-probe guards per set (rk_batch.hip)
+  if (ctx->batch_tables) rk::batch_nbd(*ctx->batch_tables, false, w.cx, m, pl.nbx, st);
   HIPCHK(ctx, hipGetLastError());
   mark(ctx, RK_PH_OCC_CSR);
   // pending counters: the X axis' at ctrl[64..), the Y axis' after them (both
@@ -703,6 +705,8 @@ int classify_narrow(rk_ctx *ctx, const rk_frags_soa *in, const rk_params *prms, 
                             w.xbits, st);
     } else  // later ratio pairs, or a repeat: the same CSR, new X results
       rk::nw_fill_y(w.cy.ent, w.xbits, w.cy.state, m, st);
+    if (ctx->batch_tables && q == 0 && attempt == 0)  // (the CSR persists across attempts)
+      rk::batch_nbd(*ctx->batch_tables, true, w.cy, m, pl.nby, st);
     rk::Axis ay{w.cy.key, w.cy.ent, nullptr, nullptr, w.cy.state, nullptr, w.par,
                 w.cy.pk, w.cy.nbd, w.rlen_at, w.rbeg_at, m, pl.max_y, pq.len_ratio,
                 pq.pos_ratio};
@@ -1134,6 +1138,7 @@ extern "C" void rk_destroy(rk_ctx *ctx) {
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
   if (ctx->stream2) (void)hipStreamSynchronize(ctx->stream2);
   rk::io_destroy(ctx);
+  rk::batch_destroy(ctx);
   if (ctx->ws) (void)hipFree(ctx->ws);
   if (ctx->io) (void)hipFree(ctx->io);
   if (ctx->ws_wide) (void)hipFree(ctx->ws_wide);

@@ -20,7 +20,15 @@
 // copies; default rccl, local with --same-device), --save-soa PATH (after the
 // parse, keep the database as a binary SoA cache), --soa (the input is such a
 // cache: no parse at all).
+//
+//   rk_repkiller --batch <list> <len_ratio> <pos_ratio>
+//
+// <list> holds one "input.csv<TAB>output.csv" per line: the inputs are loaded
+// (at most 16 threads), classified together by ONE rk_classify_batch call and
+// each output written as a run of its own would write it.
+#include <atomic>
 #include <chrono>
+#include <fstream>
 #include <thread>
 #include <cstdio>
 #include <cstdlib>
@@ -36,6 +44,8 @@ static void print_help() {
   std::printf("Usage: ./rk_repkiller [--device N] [--gpus P [--same-device] [--comm rccl|local]] "
               "[--timing] [--save-soa cache.soa | --soa] <input_file_path> <output_file_path> "
               "<length_ratio> <position_ratio> [<length_ratio> <position_ratio>]...\n");
+  std::printf("       ./rk_repkiller [--device N] --batch <list of input<TAB>output lines> "
+              "<length_ratio> <position_ratio>\n");
   std::fflush(stdout);
 }
 
@@ -110,10 +120,103 @@ static int classify_sharded_threads(const rk_frags_soa &soa, int device, int gpu
   return 0;
 }
 
+// --batch: every listed CSV through one batched classification
+static int run_batch(const char *list_path, double lr, double pr, int device) {
+  std::ifstream lf(list_path);
+  if (!lf) {
+    std::fprintf(stderr, "Could not open batch list %s.\n", list_path);
+    return 1;
+  }
+  std::vector<std::string> ins, outs;
+  for (std::string line; std::getline(lf, line);) {
+    if (!line.empty() && line.back() == '\r') line.pop_back();
+    if (line.empty()) continue;
+    const size_t tab = line.find('\t');
+    if (tab == std::string::npos || tab == 0 || tab + 1 == line.size()) {
+      std::fprintf(stderr, "Batch list line without input<TAB>output: %s\n", line.c_str());
+      return 1;
+    }
+    ins.push_back(line.substr(0, tab));
+    outs.push_back(line.substr(tab + 1));
+  }
+  const size_t ns = ins.size();
+  std::printf("--- Running REPKILLER (MI355X), %zu fragment sets ---\n\n", ns);
+  std::fflush(stdout);
+  std::vector<rk_db *> dbs(ns, nullptr);
+  std::vector<int> lrc(ns, 0);
+  {
+    std::atomic<size_t> next{0};
+    std::vector<std::thread> th;
+    const size_t nt = ns < 16 ? ns : 16;
+    for (size_t t = 0; t < nt; ++t)
+      th.emplace_back([&] {
+        for (size_t k; (k = next++) < ns;) lrc[k] = rk_db_load_csv(ins[k].c_str(), &dbs[k]);
+      });
+    for (auto &t : th) t.join();
+  }
+  auto free_all = [&] {
+    for (rk_db *d : dbs) rk_db_free(d);
+  };
+  for (size_t k = 0; k < ns; ++k)
+    if (lrc[k]) {
+      if (lrc[k] == RK_E_IO) std::fprintf(stderr, "Could not open input file %s.\n", ins[k].c_str());
+      else if (lrc[k] == RK_E_COUNT) std::fprintf(stderr, "Unexpected number of fragments\n");
+      else std::fprintf(stderr, "loading %s failed (%d)\n", ins[k].c_str(), lrc[k]);
+      free_all();
+      return 1;
+    }
+  std::vector<uint64_t> off(ns + 1, 0), hx(ns), hy(ns), n_out(ns), n_groups(ns);
+  std::vector<rk_frags_soa> views(ns);
+  for (size_t k = 0; k < ns; ++k) {
+    uint64_t total;
+    rk_db_view(dbs[k], &views[k], &hx[k], &hy[k], &total);
+    off[k + 1] = off[k] + views[k].n;
+  }
+  const uint64_t n = off[ns];
+  std::vector<uint64_t> x(n), y(n), len(n);
+  std::vector<uint8_t> strand(n), rep(n);
+  std::vector<uint32_t> gid(n), order(n);
+  for (size_t k = 0; k < ns; ++k)
+    if (views[k].n) {
+      std::memcpy(x.data() + off[k], views[k].x_start, views[k].n * 8);
+      std::memcpy(y.data() + off[k], views[k].y_start, views[k].n * 8);
+      std::memcpy(len.data() + off[k], views[k].length, views[k].n * 8);
+      std::memcpy(strand.data() + off[k], views[k].strand, views[k].n);
+    }
+  rk_ctx *ctx = nullptr;
+  int rc = rk_create(&ctx, device);
+  if (rc) {
+    std::fprintf(stderr, "no usable gfx950 device %d (%d)\n", device, rc);
+    free_all();
+    return 1;
+  }
+  const rk_frags_soa soa{x.data(), y.data(), len.data(), strand.data(), n};
+  const rk_batch_params bp{(uint32_t)ns, off.data(), hx.data(), hy.data(), lr, pr};
+  rk_batch_result br{order.data(), gid.data(), rep.data(), n_out.data(), n_groups.data()};
+  rc = rk_classify_batch(ctx, &soa, &bp, &br);
+  if (rc) {
+    std::fprintf(stderr, "classification failed (%d): %s\n", rc, rk_last_error(ctx));
+    rk_destroy(ctx);
+    free_all();
+    return 1;
+  }
+  rk_destroy(ctx);
+  for (size_t k = 0; k < ns && !rc; ++k) {
+    const rk_result r{order.data() + off[k], gid.data() + off[k], rep.data() + off[k], n_out[k],
+                      n_groups[k]};
+    if ((rc = rk_db_write_csv(dbs[k], outs[k].c_str(), &r)))
+      std::fprintf(stderr, "writing %s failed (%d)\n", outs[k].c_str(), rc);
+  }
+  free_all();
+  if (rc) return 1;
+  std::printf("Repkiller finished with no errors\n");
+  return 0;
+}
+
 int main(int argc, char **argv) {
   int device = 0, gpus = 1;
   bool timing = false, same_device = false, soa_in = false;
-  const char *comm_kind = nullptr, *save_soa = nullptr;
+  const char *comm_kind = nullptr, *save_soa = nullptr, *batch_list = nullptr;
   std::vector<const char *> pos;
   for (int i = 1; i < argc; ++i) {
     if (!std::strcmp(argv[i], "--device") && i + 1 < argc) device = std::atoi(argv[++i]);
@@ -123,6 +226,7 @@ int main(int argc, char **argv) {
     else if (!std::strcmp(argv[i], "--timing")) timing = true;
     else if (!std::strcmp(argv[i], "--soa")) soa_in = true;
     else if (!std::strcmp(argv[i], "--save-soa") && i + 1 < argc) save_soa = argv[++i];
+    else if (!std::strcmp(argv[i], "--batch") && i + 1 < argc) batch_list = argv[++i];
     else pos.push_back(argv[i]);
   }
   if (gpus < 1 || gpus > 32 ||
@@ -130,6 +234,16 @@ int main(int argc, char **argv) {
     std::fprintf(stderr, "Invalid --gpus / --comm.\n");
     print_help();
     return 1;
+  }
+  if (batch_list) {
+    double lr, pr;
+    if (pos.size() != 2 || !parse_ratio(pos[0], &lr) || !parse_ratio(pos[1], &pr) || lr <= 0 ||
+        pr <= 0 || gpus != 1) {
+      std::fprintf(stderr, "--batch takes a list file and one positive ratio pair.\n");
+      print_help();
+      return 1;
+    }
+    return run_batch(batch_list, lr, pr, device);
   }
   const bool local = comm_kind ? !std::strcmp(comm_kind, "local") : same_device;
   // init_args (commonFunctions.cpp:14-29)

@@ -14,6 +14,14 @@
 
 namespace rk {
 struct IoEngine;  // rk_io.hip: copy stream, pinned staging ring, host copy threads
+struct BatchState;  // rk_batch.hip: tables, scratch and events of rk_classify*_batch
+// Device tables of the sub-batch being classified combined (rk_batch.hip): the
+// record pipeline corrects the upward-probe codes of both axes with them
+struct BatchTables {
+  uint32_t nsets;
+  const uint32_t *bkt_x, *bkt_y;  // window starts in 100-bp buckets, nsets + 1 each
+  const uint32_t *mi_x, *mi_y;    // every set's own max_index (seq_size / 100)
+};
 }
 
 // Grow-only device buffers of the sharded driver, one per slot (the exchange
@@ -47,6 +55,10 @@ struct rk_ctx {
   size_t io_cap = 0;
   rk::IoEngine *ioe = nullptr;
   rk_pool pool;  // rk_classify_sharded buffers
+  rk::BatchState *batch = nullptr;  // rk_classify*_batch buffers
+  // non-null only while a batch's combined set is being classified
+  const rk::BatchTables *batch_tables = nullptr;
+  rk_batch_stats batch_stats{};
   // the sharded driver's fast path (rk_shard_fast.h): its all-gather messages
   // (pinned, every rank's), the stage fingerprints of the last call that
   // completed on it (a stage whose gathered counts match needs no agreement
@@ -141,6 +153,13 @@ int readback(rk_ctx *ctx, const uint32_t *dev, uint32_t count);
 void collect_kernel_timing(rk_ctx *ctx);
 // device error bits (ERRB_*) -> status + message
 int err_status(rk_ctx *ctx, uint32_t bits);
+
+// rk_batch.hip: the per-set upward-probe guards of a combined set's axis
+// (c < max_index, c < max_index - 1 compare a position with the SET's bucket
+// count, SequenceOcupationList.cpp:58,80), rewritten into the CSR's nbd bytes
+void batch_nbd(const BatchTables &t, bool y_axis, const Csr &c, uint32_t m, uint32_t nb,
+               hipStream_t st);
+void batch_destroy(rk_ctx *ctx);
 
 // Device scratch of the occupancy sweeps for an axis of up to m entries.
 struct SweepScratch {
