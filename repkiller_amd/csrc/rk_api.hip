@@ -57,7 +57,8 @@ void collect_kernel_timing(rk_ctx *ctx) {
         double mem = 0;
         for (uint32_t b = 0; b < nb; ++b) mem += h[(size_t)u * nb + b];
         const int sl = ctx->kt.tier_slot[u];
-        if (sl >= 0 && sl < ctx->kt.n) ctx->kt.bytes[sl] = 12.0 * mem;
+        if (sl >= 0 && sl < ctx->kt.n)
+          ctx->kt.bytes[sl] = (u == GS_NTIER - 1 ? 12.0 : ctx->kt.tier_member_bytes) * mem;
         const int s2 = u == GS_NTIER - 1 ? ctx->kt.tier_slot[GS_NTIER] : -1;  // phase B
         if (s2 >= 0 && s2 < ctx->kt.n) ctx->kt.bytes[s2] = 12.0 * mem;
       }
@@ -365,7 +366,7 @@ struct NWork {
   uint4 *Ra, *Rb, *yrec, *erec;
   rk::Csr cx, cy;
   uint32_t *xpos, *xbits;
-  uint32_t *par, *isnew, *newrank, *sgid, *tag, *otag, *mrow, *goff;
+  uint32_t *par, *isnew, *newrank, *tag, *otag, *mrow, *goff;  // (gids: the caller's array)
   uint64_t *reckey;
   void *gsort;
   uint32_t *rpend, *runs, *rlen_at, *rbeg_at;
@@ -400,7 +401,6 @@ size_t carve_nw(Carve &c, uint64_t n1, uint32_t nbx, NWork &w) {
   w.par = c.take<uint32_t>(n);
   w.isnew = c.take<uint32_t>(n);
   w.newrank = c.take<uint32_t>(n);
-  w.sgid = c.take<uint32_t>(n);
   w.tag = c.take<uint32_t>(n);
   w.otag = c.take<uint32_t>(n);
   w.mrow = c.take<uint32_t>(n);
@@ -665,6 +665,12 @@ int classify_narrow(rk_ctx *ctx, const rk_frags_soa *in, const rk_params *prms, 
     const int v = e ? atoi(e) : 3;
     return (uint32_t)(v < 1 ? 1 : v > 8 ? 8 : v);
   }();
+  // RK_EMIT_DIRECT=0: the group sort writes tags (otag) in every tier and one
+  // pass over all members (emit_result) turns them into the result
+  static const bool emit_direct = [] {
+    const char *e = getenv("RK_EMIT_DIRECT");
+    return !(e && e[0] == '0');
+  }();
   for (uint32_t q = 0; q < npairs; ++q) {
     const rk_params &pq = prms[q];
     rk_result *out = &outs[q];
@@ -806,29 +812,46 @@ int classify_narrow(rk_ctx *ctx, const rk_frags_soa *in, const rk_params *prms, 
       rk::nw_assign(w.par, w.newrank, w.isnew, m, msplit ? mp.coarse : ed, w.ehist, st);
 
     // members (stable by gid => processing order), in-group order, flags
+    // The last member pass writes the group ids straight into the caller's
+    // array (the pair's own), which the passes below read as the group of every
+    // slot.  Direct emit (the default): the pass that finds the group starts
+    // also writes the flags and the singletons' rows, the tiers up to 2048
+    // members store rows instead of tags, and only larger groups' rows follow
+    // from otag (emit_large_groups) -- no pass over all members after the sort.
+    uint32_t *const sgid = out->gid;
+    const rk::DirectEmit de{w.mrow, out->out_order};
     if (prof) mark(ctx, RK_PH_MEMBERS);
     if (msplit) {
       // (the order records and the Y records are done with)
       rk::nw_member_sort_split(w.erec, w.isnew, w.Ra, w.Rb, w.yrec, m, G, mp, w.ehist, w.astatus,
-                               w.sgid, w.reckey, w.tag, w.mrow, w.goff, w.chist, w.coff, ss, st);
+                               sgid, w.reckey, w.tag, w.mrow, w.goff, w.chist, w.coff, ss, st);
+      // (the segment kernel knows a start but not the next position's gid: the
+      // flags and the singletons as a pass of their own)
+      if (emit_direct)
+        rk::group_offsets_emit(sgid, m, G, nullptr, w.mrow, out->repval, out->out_order, st);
     } else {
-      rk::nw_member_sort(w.erec, w.isnew, w.Ra, w.Rb, m, ed, w.ehist, w.astatus, w.sgid,
+      rk::nw_member_sort(w.erec, w.isnew, w.Ra, w.Rb, m, ed, w.ehist, w.astatus, sgid,
                          w.reckey, w.tag, w.mrow, narrow_keys, st);
-      rk::group_offsets(w.sgid, m, G, w.goff, st);
+      if (emit_direct)
+        rk::group_offsets_emit(sgid, m, G, w.goff, w.mrow, out->repval, out->out_order, st);
+      else
+        rk::group_offsets(sgid, m, G, w.goff, st);
     }
     if (prof) mark(ctx, RK_PH_GROUP_SORT);
     // one pair: the depth-limit heap segments' count (crafted inputs only)
     // comes back with the final status word (ctrl[33]) instead of a wait of
     // its own (several pairs share the scratch: each waits)
-    if ((rc = rk::sort_groups_exact(w.sgid, w.goff, G, m, w.reckey, w.tag, w.otag, w.gsort, ss,
+    if ((rc = rk::sort_groups_exact(sgid, w.goff, G, m, w.reckey, w.tag, w.otag, w.gsort, ss,
                                     ctx->host + 128, narrow_keys, st, st2, ctx->fork, ctx->join,
-                                    npairs == 1 ? w.ctrl + 33 : nullptr))) {
+                                    npairs == 1 ? w.ctrl + 33 : nullptr,
+                                    emit_direct ? &de : nullptr))) {
       ctx->err = "depth-limit heap segments: buffer allocation failed";
       return rc;
     }
     if (prof) mark(ctx, RK_PH_EMIT);
-    rk::emit_result(w.otag, w.sgid, w.goff, w.mrow, m, out->gid, out->repval, out->out_order,
-                    st);
+    if (!emit_direct)  // (gids: read and written in place)
+      rk::emit_result(w.otag, sgid, w.goff, w.mrow, m, out->gid, out->repval, out->out_order,
+                      st);
     HIPCHK(ctx, hipGetLastError());
     if (prof) mark(ctx, RK_N_PHASES);
   }
@@ -845,8 +868,12 @@ int classify_narrow(rk_ctx *ctx, const rk_frags_soa *in, const rk_params *prms, 
       ctx->err = "depth-limit heap segments: buffer allocation failed";
       return rc;
     }
-    rk::emit_result(w.otag, w.sgid, w.goff, w.mrow, m, outs[0].gid, outs[0].repval,
-                    outs[0].out_order, st);
+    if (emit_direct)  // the heap segments lie in groups above 2048 members: those groups' rows
+      rk::emit_large_groups(G, m, w.goff, w.otag, w.gsort,
+                            rk::DirectEmit{w.mrow, outs[0].out_order}, st);
+    else
+      rk::emit_result(w.otag, outs[0].gid, w.goff, w.mrow, m, outs[0].gid, outs[0].repval,
+                      outs[0].out_order, st);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipEventRecord(ctx->ev1, st));
     if ((rc = readback(ctx, w.ctrl, 1))) return rc;

@@ -197,6 +197,72 @@ __global__ void __launch_bounds__(256) k_group_offsets(const uint32_t *sgid, uin
   if (blockIdx.x == 0 && threadIdx.x == 0) goff[ngroups] = m;
 }
 
+// group_offsets_emit: the starts as above, plus what the result needs from
+// them alone.  Position t is a start when its gid differs from t - 1's, and its
+// group ends there when t + 1 is another start or m: flag 0 for a start that is
+// also an end (a singleton, whose file row goes straight to out_order), 1 for
+// another start, 2 otherwise.  Only positions below m are written.
+__global__ void k_group_offsets_emit_unaligned(const uint32_t *sgid, uint32_t m,
+                                               uint32_t ngroups, uint32_t *goff,
+                                               const uint32_t *mrow, uint8_t *out_rep,
+                                               uint32_t *out_order) {
+  GRID_STRIDE(q, m) {
+    const uint32_t g = sgid[q];
+    const bool start = q == 0 || g != sgid[q - 1];
+    const bool end = q + 1 == m || sgid[q + 1] != g;
+    if (start && goff) goff[g] = q;
+    out_rep[q] = start ? (end ? 0 : 1) : 2;
+    if (start && end) out_order[q] = mrow[q];
+  }
+  if (goff && blockIdx.x == 0 && threadIdx.x == 0) goff[ngroups] = m;
+}
+// four positions per thread (sgid 16-B aligned): the quad's gids in one load,
+// the gid before and the gid after it one word each; the four flags go out as
+// one word when out_rep is 4-B aligned (rep_word)
+__global__ void __launch_bounds__(256) k_group_offsets_emit(const uint32_t *sgid, uint32_t m,
+                                                             uint32_t ngroups, uint32_t *goff,
+                                                             const uint32_t *mrow,
+                                                             uint8_t *out_rep, uint32_t *out_order,
+                                                             bool rep_word) {
+  const uint32_t nq = (m + 3) / 4;
+  for (uint32_t t = blockIdx.x * blockDim.x + threadIdx.x; t < nq; t += gridDim.x * blockDim.x) {
+    const uint32_t q0 = t * 4;
+    const bool full = q0 + 4 <= m;
+    uint32_t g[5];
+    if (full) {
+      const uint4 v = *reinterpret_cast<const uint4 *>(sgid + q0);
+      g[0] = v.x, g[1] = v.y, g[2] = v.z, g[3] = v.w;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) g[j] = q0 + j < m ? sgid[q0 + j] : 0u;
+    }
+    g[4] = q0 + 4 < m ? sgid[q0 + 4] : 0u;
+    uint32_t prev = q0 ? sgid[q0 - 1] : ~0u;
+    uint32_t word = 0;
+    uint8_t f[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const uint32_t q = q0 + j;
+      const bool in = q < m;
+      const bool start = g[j] != prev;
+      const bool end = q + 1 >= m || g[j + 1] != g[j];
+      if (in && start && goff) goff[g[j]] = q;
+      f[j] = start ? (end ? 0 : 1) : 2;
+      word |= (uint32_t)f[j] << (8 * j);
+      if (in && start && end) out_order[q] = mrow[q];
+      prev = g[j];
+    }
+    if (full && rep_word) {
+      *reinterpret_cast<uint32_t *>(out_rep + q0) = word;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (q0 + j < m) out_rep[q0 + j] = f[j];
+    }
+  }
+  if (goff && blockIdx.x == 0 && threadIdx.x == 0) goff[ngroups] = m;
+}
+
 // Every thread follows its parent chain towards the root (up to 32 links per
 // round) and stores what it reached; other threads compress the same chains
 // concurrently, which only ever replaces a parent by one of its ancestors.
@@ -367,6 +433,20 @@ void group_offsets(const uint32_t *sgid, uint32_t m, uint32_t ngroups, uint32_t 
   else
     k_group_offsets_unaligned<<<grid_for(m, 256), 256, 0, st>>>(sgid, m, ngroups, goff);
   kt_end(st, KID_GROUP_OFFSETS, 4.0 * m + 4.0 * ngroups);
+}
+void group_offsets_emit(const uint32_t *sgid, uint32_t m, uint32_t ngroups, uint32_t *goff,
+                        const uint32_t *mrow, uint8_t *out_rep, uint32_t *out_order,
+                        hipStream_t st) {
+  kt_begin(st, KID_GROUP_OFFSETS);
+  if ((reinterpret_cast<uintptr_t>(sgid) & 15) == 0)
+    k_group_offsets_emit<<<grid_for((m + 3) / 4, 256, 16384), 256, 0, st>>>(
+        sgid, m, ngroups, goff, mrow, out_rep, out_order,
+        (reinterpret_cast<uintptr_t>(out_rep) & 3) == 0);
+  else
+    k_group_offsets_emit_unaligned<<<grid_for(m, 256), 256, 0, st>>>(sgid, m, ngroups, goff, mrow,
+                                                                     out_rep, out_order);
+  // gid in, flag out; the starts; a singleton's row in and out (one per group at most)
+  kt_end(st, KID_GROUP_OFFSETS, 5.0 * m + (goff ? 4.0 : 0.0) * ngroups + 8.0 * ngroups);
 }
 void jump_round(Proc p, uint32_t m, uint32_t *changed, uint32_t *isnew, uint32_t *err,
                 hipStream_t st, const uint32_t *open) {

@@ -24,13 +24,16 @@
 //     neighbours, so __final_insertion_sort == a stable sort inside each leaf:
 //     every element's final slot is its stable rank inside its leaf.
 //
-// Tiers (chosen per group by size): 1..16 members -> one thread per member
-// (insertion sort == stable rank); 17..64 -> one wavefront per group entirely
+// Tiers (chosen per group by size): 2..16 members -> one thread per member
+// (insertion sort == stable rank; 4 lanes per group up to 4 members, 16
+// above); 17..64 -> one wavefront per group entirely
 // in registers; 65..512 and 513..2048 -> one wavefront per group with the
 // group staged in LDS (12 KB / 45 KB per wave); larger -> the same wavefront
 // code on global memory.  Segments of <= 64 inside the larger tiers are
 // finished in registers as well.
-// In every tier the result goes to `otag` (member order, group-major).
+// In every tier the result goes to `otag` (member order, group-major) -- or,
+// for the tiers up to 2048 members of a caller with a DirectEmit, the file row
+// of every ranked member straight to the output order (RowSink).
 #include "rk_internal.h"
 
 #include <algorithm>
@@ -55,6 +58,21 @@ __device__ __forceinline__ void wave_sync_global() {
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
 }
+
+// Where a ranked member goes: its tag at its slot (the default), or the file
+// row of that tag (the record pipeline's direct emit: no pass over otag after
+// the sort).  A tag is stored only when it is final.
+struct TagSink {
+  uint32_t *out;
+  __device__ __forceinline__ void put(uint32_t slot, uint32_t tag) const { out[slot] = tag; }
+  __device__ __forceinline__ TagSink at(uint32_t b) const { return TagSink{out + b}; }
+};
+struct RowSink {
+  uint32_t *out;
+  const uint32_t *rows;
+  __device__ __forceinline__ void put(uint32_t slot, uint32_t tag) const { out[slot] = rows[tag]; }
+  __device__ __forceinline__ RowSink at(uint32_t b) const { return RowSink{out + b, rows}; }
+};
 
 template <bool GLOBAL>
 __device__ __forceinline__ void sync_mem() {
@@ -573,9 +591,9 @@ __device__ void reg_sort_core(const V &v, bool in, uint32_t mpos, int &sf, int &
 // 32-bit registers (half the shuffle traffic).  The final order -- stable
 // leaf ranks, or heap-sorted ranges in place -- is written to out[] and the
 // positions are marked B = 3.
-template <bool GLOBAL, class KT, class V>
+template <bool GLOBAL, class KT, class V, class SK>
 __device__ void reg_finish(const V &v, bool in, int bl, uint32_t bm, int len, int d,
-                           uint32_t lane, uint64_t k64, uint32_t t, uint32_t *out,
+                           uint32_t lane, uint64_t k64, uint32_t t, const SK &out,
                            uint32_t tbase) {
   const int x = (int)lane;
   KT k = in ? (KT)k64 : (KT)~(KT)0;
@@ -592,23 +610,23 @@ __device__ void reg_finish(const V &v, bool in, int bl, uint32_t bm, int len, in
     r += (j < my) && (ky < k || (ky == k && y < x));
   }
   if (in) {
-    out[heaped ? mpos : bm + (uint32_t)(sf - bl) + r] = tbase + t;
+    out.put(heaped ? mpos : bm + (uint32_t)(sf - bl) + r, tbase + t);
     if (v.B) v.B[mpos] = 3;
   }
 }
 
-template <bool GLOBAL, class V>
+template <bool GLOBAL, class V, class SK>
 __device__ void reg_batch(const V &v, bool in, int bl, uint32_t bm, int len, int d,
-                          uint32_t lane, uint32_t *out, uint32_t tbase = 0) {
+                          uint32_t lane, const SK &out, uint32_t tbase = 0) {
   const uint32_t mpos = bm + (uint32_t)((int)lane - bl);
   const uint64_t k = in ? (uint64_t)v.K[mpos] : ~0ull;
   // the group arrays' tags are positions (tag[x] == x, sort_groups_exact):
   // not read from memory; LDS views hold the moved tags
   const uint32_t t = in ? (GLOBAL ? mpos : v.T[mpos]) : 0u;
   if (sizeof(typename V::key_t) == 8 && __ballot(in && (k >> 32) != 0))
-    reg_finish<GLOBAL, uint64_t, V>(v, in, bl, bm, len, d, lane, k, t, out, tbase);
+    reg_finish<GLOBAL, uint64_t, V, SK>(v, in, bl, bm, len, d, lane, k, t, out, tbase);
   else
-    reg_finish<GLOBAL, uint32_t, V>(v, in, bl, bm, len, d, lane, k, t, out, tbase);
+    reg_finish<GLOBAL, uint32_t, V, SK>(v, in, bl, bm, len, d, lane, k, t, out, tbase);
 }
 
 // The lanes that sort one group: the whole wavefront (W = 64), or one half of
@@ -796,9 +814,9 @@ __device__ unsigned long long g_gs_prof[8];
 #endif
 
 // the whole libstdc++ std::sort of one group [0, n) of view v, then stable
-// leaf ranks written to out[0..n) (tags only)
-template <bool GLOBAL, class V, int W = 64>
-__device__ void wave_std_sort(const V &v, uint32_t n, uint32_t *out, Frame *stack,
+// leaf ranks written to the sink's slots 0..n) (tags, or their rows)
+template <bool GLOBAL, class V, int W = 64, class SK>
+__device__ void wave_std_sort(const V &v, uint32_t n, const SK &out, Frame *stack,
                               Frame *smallq, Frame *heapq, GLanes<W> L, int d0,
                               uint32_t reg_max, uint32_t tbase = 0, bool small_part = true) {
   static_assert(W == 64 || W == 32, "a wavefront or a half");
@@ -893,7 +911,7 @@ __device__ void wave_std_sort(const V &v, uint32_t n, uint32_t *out, Frame *stac
     if (bd) carry = c + 63 - (uint32_t)__clzll(bd);
     if (x < n && b != 3) {
       if (b == 2) {
-        out[x] = tbase + v.T[x];
+        out.put(x, tbase + v.T[x]);
       } else {
         const typename V::key_t kx = v.K[x];
         uint32_t r = 0;
@@ -906,7 +924,7 @@ __device__ void wave_std_sort(const V &v, uint32_t n, uint32_t *out, Frame *stac
         for (int j = 0; j < THRESH; ++j)
           r += (uint32_t)(s + j < e) &
                ((uint32_t)(ky[j] < kx) | ((uint32_t)(ky[j] == kx) & (uint32_t)(s + j < x)));
-        out[s + r] = tbase + v.T[x];
+        out.put(s + r, tbase + v.T[x]);
       }
     }
   }
@@ -925,8 +943,8 @@ __device__ void wave_std_sort(const V &v, uint32_t n, uint32_t *out, Frame *stac
 #endif
 }
 
-// The listed tiers' groups, tier-major in one array: tier u (1..6) owns
-// list[off[(u-1)*nblk] .. off[u*nblk]) (off = exclusive scan of per-block
+// The listed tiers' groups, tier-major in one array: tier u owns
+// list[off[u*nblk] .. off[(u+1)*nblk]) (off = exclusive scan of per-block
 // tier counts, see k_tier_lists).  Kernels read their range on the device, so
 // no host round trip sizes the launches.
 struct TierLists {
@@ -944,10 +962,10 @@ struct TierLists {
 // own segment, so the groups never mix).  The introsort runs there and
 // __final_insertion_sort is the stable rank inside each leaf (<= 16 lanes,
 // by shuffles); heap-sorted ranges are already in order.
-template <int PACK>
+template <int PACK, class SK>
 __global__ void __launch_bounds__(256) k_sort_groups_reg(TierLists tl, int tier,
                                                          const uint32_t *goff, uint64_t *key,
-                                                         uint32_t *tag, uint32_t *otag) {
+                                                         uint32_t *tag, SK otag) {
   constexpr int SPAN = 64 / PACK;
   const uint32_t lane = threadIdx.x & 63;
   const int j = (int)lane / SPAN;
@@ -975,12 +993,12 @@ __host__ __device__ constexpr uint32_t lds_stack(uint32_t cap) {
 // bytes (a CU holds a bounded number of blocks, so one-wave blocks of the
 // small caps leave it with few resident wavefronts)
 // (W = 32: each half of a wavefront sorts its own group in its own slab)
-template <class KT, int WPB, int W = 64>
+template <class KT, int WPB, int W = 64, class SK = TagSink>
 __global__ void __launch_bounds__(64 * WPB)
 __attribute__((amdgpu_waves_per_eu(W == 32 && sizeof(KT) == 4 ? 8 : 1))) k_sort_groups_lds(TierLists tl, int tier,
                                                               const uint32_t *goff,
                                                               const uint64_t *key,
-                                                              const uint32_t *tag, uint32_t *otag,
+                                                              const uint32_t *tag, SK otag,
                                                               uint32_t cap, uint32_t reg_max,
                                                               uint32_t slab, bool small_part) {
   extern __shared__ __align__(16) uint8_t smem_all[];
@@ -1014,7 +1032,7 @@ __attribute__((amdgpu_waves_per_eu(W == 32 && sizeof(KT) == 4 ? 8 : 1))) k_sort_
       T[x] = (uint16_t)x;  // tags are positions (the output adds b)
     }
     wave_sync();
-    wave_std_sort<false, ViewT<KT, uint16_t, uint16_t>, W>(v, n, otag + b, stack, smallq, heapq,
+    wave_std_sort<false, ViewT<KT, uint16_t, uint16_t>, W>(v, n, otag.at(b), stack, smallq, heapq,
                                                            L, 2 * (31 - __clz((int)n)), reg_max,
                                                            b, small_part);
     wave_sync();
@@ -2283,50 +2301,57 @@ __global__ void __launch_bounds__(64 * WPB) k_sort_segments(TierLists tl, int ti
         T[y] = tag[x + y];
       }
       wave_sync();
-      wave_std_sort<false>(v, n, otag + x, stack, smallq, heapq, GLanes<64>{lane, 0u},
+      wave_std_sort<false>(v, n, TagSink{otag + x}, stack, smallq, heapq, GLanes<64>{lane, 0u},
                            (int)(h >> 16), reg_max, 0u, small_part);
       wave_sync();
     }
   }
 }
 
-// Groups of 2..16 members (tier 0): __final_insertion_sort alone sorts them,
-// so a member's final slot is its stable rank inside the group.  Sixteen
-// lanes per group, four groups per wavefront: lane l loads member l (the
-// group's members are contiguous), ranks itself against the other lanes of
-// its segment by width-16 shuffles and writes its tag at its rank.
+// Groups of 2..16 members (tiers 0 and 1): __final_insertion_sort alone sorts
+// them, so a member's final slot is its stable rank inside the group.  LANES
+// lanes per group -- 4 for the groups of 2..4 members (sixteen groups per
+// wavefront: most small groups are pairs, and sixteen lanes each left three
+// quarters of a wavefront idle), 16 for 5..16 (four groups per wavefront):
+// lane l loads member l (the group's members are contiguous), ranks itself
+// against the other lanes of its segment by width-LANES shuffles and writes
+// its tag at its rank.
 // Singletons are not listed and not written: emit_result takes a one-member
 // group's slot as it is (tag[x] == x for every caller).
-__global__ void __launch_bounds__(256) k_sort_small(TierLists tl, const uint32_t *goff,
+template <int LANES, class SK>
+__global__ void __launch_bounds__(256) k_sort_small(TierLists tl, int tier, const uint32_t *goff,
                                                     const uint64_t *key, const uint32_t *tag,
-                                                    uint32_t *otag) {
+                                                    SK otag) {
+  static_assert(LANES == 4 || LANES == 16, "lanes per group");
+  constexpr int LG = LANES == 4 ? 2 : 4;
   uint32_t lo, hi;
-  tl.range(0, lo, hi);
-  const uint32_t l = threadIdx.x & 15;
-  for (uint32_t w = lo + ((blockIdx.x * blockDim.x + threadIdx.x) >> 4); w - lo < hi - lo;
-       w += (gridDim.x * blockDim.x) >> 4) {
+  tl.range(tier, lo, hi);
+  const uint32_t l = threadIdx.x & (LANES - 1);
+  for (uint32_t w = lo + ((blockIdx.x * blockDim.x + threadIdx.x) >> LG); w - lo < hi - lo;
+       w += (gridDim.x * blockDim.x) >> LG) {
     const uint32_t g = tl.list[w];
     const uint32_t b = goff[g], n = goff[g + 1] - b;
     const bool in = l < n;
     const uint64_t k = in ? key[b + l] : ~0ull;
     uint32_t r = 0;
 #pragma unroll
-    for (int j = 0; j < THRESH; ++j) {
-      const uint64_t kj = __shfl(k, j, 16);
+    for (int j = 0; j < LANES; ++j) {
+      const uint64_t kj = __shfl(k, j, LANES);
       r += (uint32_t)j < n && (kj < k || (kj == k && (uint32_t)j < l));
     }
-    if (in) otag[b + r] = b + l;  // tags are positions
+    if (in) otag.put(b + r, b + l);  // tags are positions
   }
 }
 
-// Tiers by group size (singletons: none): 0 = 2..16 members (k_sort_small), 1 =
-// 17..32 (registers, two groups per wavefront), 2 = 33..64 (registers), 3..6
-// = up to LDS_CAPS[t-3] (LDS), 7 = larger (global memory).  Small LDS caps
+// Tiers by group size (singletons: none): 0 = 2..4 members and 1 = 5..16
+// (k_sort_small, 4 / 16 lanes per group), 2 = 17..32 (registers, two groups
+// per wavefront), 3 = 33..64 (registers), 4..7 = up to LDS_CAPS[t-4] (LDS), 8
+// = larger (global memory).  Small LDS caps
 // keep many wavefronts resident per CU (a 65..128-member group needs ~3 KB of
 // LDS, a 2048-member one ~30 KB).
 constexpr int NTIER = GS_NTIER;
 constexpr int NLDS = 4;
-constexpr int TIER_LDS0 = 3;
+constexpr int TIER_LDS0 = 4;
 static_assert(TIER_LDS0 + NLDS + 1 == NTIER, "tier layout");
 struct Caps {
   uint32_t c[NLDS];
@@ -2336,9 +2361,10 @@ __host__ __device__ constexpr Caps lds_caps() { return Caps{{128, 256, 512, 2048
 __device__ __forceinline__ int tier_of(uint32_t n) {
   constexpr Caps caps = lds_caps();
   if (n <= 1) return NTIER;  // a singleton: nothing to sort, nothing listed
-  if (n <= (uint32_t)THRESH) return 0;
-  if (n <= 32) return 1;
-  if (n <= 64) return 2;
+  if (n <= 4) return 0;
+  if (n <= (uint32_t)THRESH) return 1;
+  if (n <= 32) return 2;
+  if (n <= 64) return 3;
 #pragma unroll
   for (int j = 0; j < NLDS; ++j)
     if (n <= caps.c[j]) return TIER_LDS0 + j;
@@ -2426,6 +2452,27 @@ __global__ void __launch_bounds__(256) k_tier_lists(const uint32_t *goff, uint32
   }
 }
 
+// The direct emit's groups above the largest LDS cap: their order is in otag
+// (phase A, phase B and the heap segments write tags there), so their rows
+// follow in one pass over the largest tier's list, one block per group at a
+// time; no such group (cfg3): every block returns at once.
+// (a heap segment still to be sorted by the caller holds no tags yet: whatever
+// is there is kept inside the array, and the pass is run again afterwards)
+__global__ void __launch_bounds__(256) k_emit_listed(TierLists tl, int tier, const uint32_t *goff,
+                                                     const uint32_t *otag, DirectEmit d,
+                                                     uint32_t m) {
+  uint32_t lo, hi;
+  tl.range(tier, lo, hi);
+  for (uint32_t w = lo + blockIdx.x; w < hi; w += gridDim.x) {
+    const uint32_t g = tl.list[w];
+    const uint32_t b = goff[g], e = goff[g + 1];
+    for (uint32_t x = b + threadIdx.x; x < e; x += blockDim.x) {
+      const uint32_t o = otag[x];
+      d.out_order[x] = d.rows[o < m ? o : x];
+    }
+  }
+}
+
 // keys, 16-bit tags, PL, PR, B, frames (the register-batch queue only when
 // reg_max > 0: without it the 257..512 tier's slab is 6.3 KB, 25 resident
 // wavefronts per CU instead of 23)
@@ -2471,11 +2518,26 @@ int sort_groups_heap_deferred(uint32_t ngroups, uint32_t m, uint64_t *key, uint3
   return heap_segments(heap_queue(scratch, m, ngroups), nheap, key, tag, otag, host_words, st);
 }
 
+void emit_large_groups(uint32_t ngroups, uint32_t m, const uint32_t *goff, const uint32_t *otag,
+                       const void *scratch, DirectEmit direct, hipStream_t st) {
+  if (!m) return;
+  // (sort_groups_exact's layout: the lists after pl and pr, the scanned block
+  // counts after the counts)
+  const uint32_t nblk = (ngroups + TCH - 1) / TCH;
+  const uint32_t *list = reinterpret_cast<const uint32_t *>(scratch) + 2 * (size_t)m;
+  const uint8_t *bnd = reinterpret_cast<const uint8_t *>(
+      (reinterpret_cast<uintptr_t>(list + ngroups + 1) + 15) & ~(uintptr_t)15);
+  const uint32_t *bc = reinterpret_cast<const uint32_t *>(
+      (reinterpret_cast<uintptr_t>(bnd + m) + 63) & ~(uintptr_t)63);
+  const uint32_t *boff = bc + (size_t)NTIER * nblk + 1;
+  k_emit_listed<<<1024, 256, 0, st>>>(TierLists{list, boff, nblk}, NTIER - 1, goff, otag, direct, m);
+}
+
 int sort_groups_exact(const uint32_t *gid_sorted, const uint32_t *goff, uint32_t ngroups,
                        uint32_t m, uint64_t *key, uint32_t *tag, uint32_t *otag, void *scratch,
                        ScanScratch ss, uint32_t *host_words, bool narrow_keys, hipStream_t st,
                        hipStream_t side, hipEvent_t ev_fork, hipEvent_t ev_join,
-                       uint32_t *heap_count) {
+                       uint32_t *heap_count, const DirectEmit *direct) {
   if (!m) {
     if (heap_count) (void)hipMemsetAsync(heap_count, 0, 4, st);
     return RK_OK;
@@ -2508,8 +2570,10 @@ int sort_groups_exact(const uint32_t *gid_sorted, const uint32_t *goff, uint32_t
   k_tier_lists<<<nblk, 256, 0, st>>>(goff, ngroups, nblk, boff, list, bnd, m);
   const TierLists tl{list, boff, nblk};
   // algorithmic bytes of every tier (timing only): each member's key read, its
-  // tag (its position) written once at its final slot -- 12 B x the tier's members,
+  // tag (its position) written once at its final slot -- 12 B x the tier's members
+  // (16 B with the direct emit: the tag's row read and written instead),
   // filled in from bm when the timings are collected
+  if (timing) g_ktimer->tier_member_bytes = direct ? 16.0 : 12.0;
   if (timing && g_ktimer->only < 0) g_ktimer->tier_counts = bm;  // read back at collection
   auto tier_slot = [&](int u) {
     if (timing && g_ktimer->only < 0 && g_ktimer->n > 0) g_ktimer->tier_slot[u] = g_ktimer->n - 1;
@@ -2579,28 +2643,33 @@ int sort_groups_exact(const uint32_t *gid_sorted, const uint32_t *goff, uint32_t
     const int wp = cap <= 512 ? wpb : 1;
     const size_t slab = (lds_bytes(cap, narrow_keys ? 4 : 8, reg_max) + 15) & ~(size_t)15;
     kt_begin(sj, KID_SORT_LDS);
-    if (cap <= half_cap && 2 * slab <= 65536) {
-      if (narrow_keys)
-        k_sort_groups_lds<uint32_t, 1, 32><<<waves / 2, 64, 2 * slab, sj>>>(
-            tl, TIER_LDS0 + j, goff, key, tag, otag, cap, 0u, (uint32_t)slab, small_part);
-      else
-        k_sort_groups_lds<uint64_t, 1, 32><<<waves / 2, 64, 2 * slab, sj>>>(
-            tl, TIER_LDS0 + j, goff, key, tag, otag, cap, 0u, (uint32_t)slab, small_part);
-    } else if (wp == 4) {
-      if (narrow_keys)
-        k_sort_groups_lds<uint32_t, 4><<<waves / 4, 256, 4 * slab, sj>>>(
-            tl, TIER_LDS0 + j, goff, key, tag, otag, cap, reg_max, (uint32_t)slab, small_part);
-      else
-        k_sort_groups_lds<uint64_t, 4><<<waves / 4, 256, 4 * slab, sj>>>(
-            tl, TIER_LDS0 + j, goff, key, tag, otag, cap, reg_max, (uint32_t)slab, small_part);
-    } else {
-      if (narrow_keys)
-        k_sort_groups_lds<uint32_t, 1><<<waves, 64, slab, sj>>>(tl, TIER_LDS0 + j, goff, key, tag,
-                                                                otag, cap, reg_max, (uint32_t)slab, small_part);
-      else
-        k_sort_groups_lds<uint64_t, 1><<<waves, 64, slab, sj>>>(tl, TIER_LDS0 + j, goff, key, tag,
-                                                                otag, cap, reg_max, (uint32_t)slab, small_part);
-    }
+    auto go = [&](auto sink) {
+      using SK = decltype(sink);
+      if (cap <= half_cap && 2 * slab <= 65536) {
+        if (narrow_keys)
+          k_sort_groups_lds<uint32_t, 1, 32, SK><<<waves / 2, 64, 2 * slab, sj>>>(
+              tl, TIER_LDS0 + j, goff, key, tag, sink, cap, 0u, (uint32_t)slab, small_part);
+        else
+          k_sort_groups_lds<uint64_t, 1, 32, SK><<<waves / 2, 64, 2 * slab, sj>>>(
+              tl, TIER_LDS0 + j, goff, key, tag, sink, cap, 0u, (uint32_t)slab, small_part);
+      } else if (wp == 4) {
+        if (narrow_keys)
+          k_sort_groups_lds<uint32_t, 4, 64, SK><<<waves / 4, 256, 4 * slab, sj>>>(
+              tl, TIER_LDS0 + j, goff, key, tag, sink, cap, reg_max, (uint32_t)slab, small_part);
+        else
+          k_sort_groups_lds<uint64_t, 4, 64, SK><<<waves / 4, 256, 4 * slab, sj>>>(
+              tl, TIER_LDS0 + j, goff, key, tag, sink, cap, reg_max, (uint32_t)slab, small_part);
+      } else {
+        if (narrow_keys)
+          k_sort_groups_lds<uint32_t, 1, 64, SK><<<waves, 64, slab, sj>>>(
+              tl, TIER_LDS0 + j, goff, key, tag, sink, cap, reg_max, (uint32_t)slab, small_part);
+        else
+          k_sort_groups_lds<uint64_t, 1, 64, SK><<<waves, 64, slab, sj>>>(
+              tl, TIER_LDS0 + j, goff, key, tag, sink, cap, reg_max, (uint32_t)slab, small_part);
+      }
+    };
+    if (direct) go(RowSink{direct->out_order, direct->rows});
+    else go(TagSink{otag});
     kt_end(sj, KID_SORT_LDS, 0.0);
     tier_slot(TIER_LDS0 + j);
   };
@@ -2618,13 +2687,32 @@ int sort_groups_exact(const uint32_t *gid_sorted, const uint32_t *goff, uint32_t
   }();
   auto launch_small = [&](hipStream_t sj) {
     kt_begin(sj, KID_SORT_SMALL);
-    k_sort_small<<<2048, 256, 0, sj>>>(tl, goff, key, tag, otag);
-    kt_end(sj, KID_SORT_SMALL, 0.0);  // bytes filled in from the tier sizes at collection
-    tier_slot(0);
-    kt_begin(sj, KID_SORT_REG);
-    k_sort_groups_reg<2><<<4096, 256, 0, sj>>>(tl, 1, goff, key, tag, otag);
-    kt_end(sj, KID_SORT_REG, 0.0);
+    // RK_GS_SMALL4=0: the groups of 2..4 members with sixteen lanes each too
+    static const bool small4 = [] {
+      const char *e = getenv("RK_GS_SMALL4");
+      return !(e && e[0] == '0');
+    }();
+    auto small = [&](auto sink) {
+      using SK = decltype(sink);
+      if (small4) k_sort_small<4, SK><<<2048, 256, 0, sj>>>(tl, 0, goff, key, tag, sink);
+      else k_sort_small<16, SK><<<2048, 256, 0, sj>>>(tl, 0, goff, key, tag, sink);
+      kt_end(sj, KID_SORT_SMALL, 0.0);  // bytes filled in from the tier sizes at collection
+      tier_slot(0);
+      kt_begin(sj, KID_SORT_SMALL);
+      k_sort_small<16, SK><<<2048, 256, 0, sj>>>(tl, 1, goff, key, tag, sink);
+    };
+    if (direct) small(RowSink{direct->out_order, direct->rows});
+    else small(TagSink{otag});
+    kt_end(sj, KID_SORT_SMALL, 0.0);
     tier_slot(1);
+    kt_begin(sj, KID_SORT_REG);
+    if (direct)
+      k_sort_groups_reg<2, RowSink><<<4096, 256, 0, sj>>>(
+          tl, 2, goff, key, tag, RowSink{direct->out_order, direct->rows});
+    else
+      k_sort_groups_reg<2, TagSink><<<4096, 256, 0, sj>>>(tl, 2, goff, key, tag, TagSink{otag});
+    kt_end(sj, KID_SORT_REG, 0.0);
+    tier_slot(2);
   };
   if (!small_main || !side) launch_small(s2);
   // the 33..64-member tier on `st` after its LDS tiers (RK_GS_REG1=1, the
@@ -2637,9 +2725,13 @@ int sort_groups_exact(const uint32_t *gid_sorted, const uint32_t *goff, uint32_t
   }();
   auto launch_reg1 = [&](hipStream_t sj) {
     kt_begin(sj, KID_SORT_REG);
-    k_sort_groups_reg<1><<<4096, 256, 0, sj>>>(tl, 2, goff, key, tag, otag);
+    if (direct)
+      k_sort_groups_reg<1, RowSink><<<4096, 256, 0, sj>>>(
+          tl, 3, goff, key, tag, RowSink{direct->out_order, direct->rows});
+    else
+      k_sort_groups_reg<1, TagSink><<<4096, 256, 0, sj>>>(tl, 3, goff, key, tag, TagSink{otag});
     kt_end(sj, KID_SORT_REG, 0.0);
-    tier_slot(2);
+    tier_slot(3);
   };
   if (!reg1_main || !side) launch_reg1(s2);
   for (int pass = 0; pass < 2; ++pass) {
@@ -2759,6 +2851,9 @@ int sort_groups_exact(const uint32_t *gid_sorted, const uint32_t *goff, uint32_t
   }
   kt_end(st, KID_SORT_SEGS, 0.0);
   tier_slot(NTIER);
+  // the largest tier's groups went through otag: their rows now (a caller that
+  // defers the heap segments repeats this after sorting them)
+  if (direct) k_emit_listed<<<1024, 256, 0, st>>>(tl, NTIER - 1, goff, otag, *direct, m);
   if (side) (void)hipStreamWaitEvent(st, ev_join, 0);
   return hrc;
 }

@@ -72,8 +72,8 @@ enum KernelId : int {
   KID_SORT_HEAP, KID_NW_FINE, KID_NW_MFINE, KID_NW_YFINE, KID_COUNT
 };
 extern const char *const kKernelNames[KID_COUNT];
-// group-sort tiers (rk_groupsort.hip tier_of): <=16, <=32, <=64, four LDS caps, larger
-constexpr int GS_NTIER = 8;
+// group-sort tiers (rk_groupsort.hip tier_of): <=4, <=16, <=32, <=64, four LDS caps, larger
+constexpr int GS_NTIER = 9;
 
 struct KernelTimer {
   static constexpr int MAX = 256;
@@ -87,6 +87,9 @@ struct KernelTimer {
   const uint32_t *tier_counts;  // [tier][nblk] members per block, or null
   uint32_t tier_nblk;
   int tier_slot[TIERS];         // timer slot of each tier's launch (-1: none)
+  // algorithmic bytes per member of the tiers up to 2048 members: key in, tag
+  // out (12), or key and row in, row out (16, the direct emit)
+  double tier_member_bytes = 12.0;
   int only = -1;                // >= 0: time only this kernel's launches (rk_set_profiling)
   // launches whose work is known on the device only (k_sweep_long32: the
   // entries of the long runs it walks): the kernel adds its units into
@@ -260,6 +263,13 @@ void jump_listed(Proc p, uint32_t m, uint32_t *isnew, uint32_t *err, uint32_t *l
 void assign_gid(Proc p, uint32_t m, const uint32_t *newrank, hipStream_t st);
 void group_offsets(const uint32_t *sgid, uint32_t m, uint32_t ngroups, uint32_t *goff,
                    hipStream_t st);
+// the same pass, which also writes what the result needs from the group
+// starts alone: every position's repeat flag (singleton 0, a group's first
+// member 1, the others 2) and a singleton's file row (out_order[t] = mrow[t]);
+// goff null: the flags and the singletons only (the starts are known already)
+void group_offsets_emit(const uint32_t *sgid, uint32_t m, uint32_t ngroups, uint32_t *goff,
+                        const uint32_t *mrow, uint8_t *out_rep, uint32_t *out_order,
+                        hipStream_t st);
 // members (gmem, processing ids, group-major) -> sort keys, tags = member
 // slots, and the members' file rows IN PLACE of gmem
 void build_records(uint32_t *gmem, const ulonglong2 *hrec, uint32_t m, uint64_t *key,
@@ -277,11 +287,25 @@ size_t groupsort_scratch_bytes(uint32_t n);
 // and joined through ev_fork / ev_join.
 // Returns RK_OK, or the status of the depth-limit heap segments' own buffers
 // (RK_E_NOMEM / RK_E_HIP; only when they are sorted here, heap_count null).
+// direct (optional): the groups of 2..2048 members store the file row of every
+// ranked member (out_order[slot] = rows[tag]) and leave otag unwritten; the
+// larger groups keep otag and emit_large_groups turns it into rows (called
+// here after phase B; again by a caller that defers the heap segments).
+struct DirectEmit {
+  const uint32_t *rows;
+  uint32_t *out_order;
+};
 int sort_groups_exact(const uint32_t *gid_sorted, const uint32_t *goff, uint32_t ngroups,
                       uint32_t m, uint64_t *key, uint32_t *tag, uint32_t *otag, void *scratch,
                       ScanScratch ss, uint32_t *host_words, bool narrow_keys, hipStream_t st,
                       hipStream_t side = nullptr, hipEvent_t ev_fork = nullptr,
-                      hipEvent_t ev_join = nullptr, uint32_t *heap_count = nullptr);
+                      hipEvent_t ev_join = nullptr, uint32_t *heap_count = nullptr,
+                      const DirectEmit *direct = nullptr);
+// out_order[b + x] = rows[otag[b + x]] over the groups of the largest tier's
+// list (the lists of the last sort_groups_exact call on this scratch); returns
+// at once on the device when the list is empty
+void emit_large_groups(uint32_t ngroups, uint32_t m, const uint32_t *goff, const uint32_t *otag,
+                       const void *scratch, DirectEmit direct, hipStream_t st);
 // heap_count != nullptr: the depth-limit heap segments are not sorted, their
 // number goes to heap_count (device), and the caller, having read it back,
 // sorts them by this before using otag (RK_OK / RK_E_NOMEM / RK_E_HIP)

@@ -26,14 +26,14 @@ JOBS = [
     ("k_nw_fill_y", "Y states from the bitmask for later ratio pairs (X hits sit in the Y lists)", "5"),
     ("k_jump", "(RK_ROOTS_FUSED=0 only) chase parent chains to the root, round by round", "16"),
     ("k_nw_assign", "`k_nw_assign_jump`: after the scan of the parents' root flags, each member chases its chain (up to 32 links; longer ones listed for `k_nw_assign_rest`), writes the root back as its parent and takes gid = the root's rank, with the member-sort histograms", "20"),
-    ("k_group_offsets", "group bounds", "4"),
-    ("k_sort_small", "groups of 2..16 members (insertion sort == stable rank): 16 lanes per group from the tier list, width-16 shuffles; singletons are not touched (second stream)", "12 per member"),
-    ("k_sort_groups_reg", "17..64 members in registers (17..32: two groups per wavefront, second stream; 33..64: main stream, after its LDS tiers)", "12 per member"),
-    ("k_sort_groups_lds", "65..2048 members in LDS: partitions down to the leaves (a segment of <= 64 partitioned in registers: read once, stoppers by ballots, partners by lane permutes, written once), then the final insertion pass with ballot-found leaf bounds (257..2048: second stream, first)", "12 per member"),
+    ("k_group_offsets", "`k_group_offsets_emit`: group bounds, and from them alone every position's repeat flag and the singletons' rows (four positions per thread, the flags as one word)", "5 + 8 per singleton"),
+    ("k_sort_small", "groups of 2..16 members (insertion sort == stable rank): 16 lanes per group from the tier list, width-16 shuffles; singletons are not touched (second stream); a ranked member's file row goes to the output", "16 per member"),
+    ("k_sort_groups_reg", "17..64 members in registers (17..32: two groups per wavefront, second stream; 33..64: main stream, after its LDS tiers); rows stored, as above", "16 per member"),
+    ("k_sort_groups_lds", "65..2048 members in LDS: partitions down to the leaves (a segment of <= 64 partitioned in registers: read once, stoppers by ballots, partners by lane permutes, written once), then the final insertion pass with ballot-found leaf bounds (257..2048: second stream, first), which stores the rows", "16 per member"),
     ("k_sort_groups_split", "groups above 2048: partitions down to 512-member segments, each a block-wide Hoare scan (both cursors a chunk at a time into LDS stopper queues, pairs swapped from the queues), groups claimed largest first", "12 per member"),
     ("k_sort_segments", "those segments, one LDS wavefront each", "12 per member"),
     ("k_heap_segments", "depth-exhausted segments of >= 2048 members (median-of-3 killers only): make_heap level-parallel; sort_heap by one wavefront: all-equal keys (the killer) as a spine FIFO, else top 13 heap levels in LDS", "-"),
-    ("k_emit", "gid, flag, output order", "29"),
+    ("k_emit", "(RK_EMIT_DIRECT=0, the generic pipeline and the sharded drivers) gid, flag, output order from the sorted tags; the record pipeline runs only `k_emit_listed`, the rows of the groups above 2048 members", "29"),
 ]
 
 
