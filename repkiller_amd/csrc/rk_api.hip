@@ -738,7 +738,10 @@ int classify_narrow(rk_ctx *ctx, const rk_frags_soa *in, const rk_params *prms, 
       // count cleared first
       rk::zero_regions(st, {{q > 0 ? w.ehist : nullptr, 4096 * sizeof(uint32_t)},
                             {q > 0 ? w.ctrl + 12 : nullptr, sizeof(uint32_t)}});
-      rk::exclusive_scan_roots(w.par, m, w.newrank, ss, st, w.ctrl + 32);
+      // (each root's rank into its own parent word: a pair that repeats, a
+      // later pair and a later call rewrite every parent word in their sweeps
+      // before anything reads one)
+      rk::scan_root_ranks(w.par, m, ss, st, w.ctrl + 32);
       if ((rc = readback(ctx, w.ctrl + 5, 64 - 5 + 2 * rk::PEND_WORDS))) return rc;
       uint32_t pending = 0;
       for (uint32_t k = 0; k < 2 * rk::PEND_WORDS; ++k) pending |= ctx->host[64 - 5 + k];
@@ -806,8 +809,7 @@ int classify_narrow(rk_ctx *ctx, const rk_frags_soa *in, const rk_params *prms, 
     // (ehist: zero -- cleared at the start, or with the roots' words for q > 0)
     // gids into isnew's words (dead after the scan)
     if (fused_roots)  // (otag: free until the group sort)
-      rk::nw_assign_jump(w.par, w.newrank, w.isnew, m, msplit ? mp.coarse : ed, w.ehist, w.otag,
-                         w.ctrl, st);
+      rk::nw_assign_jump(w.par, w.isnew, m, msplit ? mp.coarse : ed, w.ehist, w.otag, w.ctrl, st);
     else
       rk::nw_assign(w.par, w.newrank, w.isnew, m, msplit ? mp.coarse : ed, w.ehist, st);
 

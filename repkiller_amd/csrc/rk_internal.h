@@ -51,10 +51,14 @@ void exclusive_scan_u32(const uint32_t *in, uint32_t *out, size_t n, ScanScratch
 // the same, in[0] cleared once read (out != in)
 void exclusive_scan_u32_clear0(uint32_t *in, uint32_t *out, size_t n, ScanScratch ss,
                                hipStream_t st);
-// out[k] = number of roots (par[j] == j) among j < k, for k <= m: the
-// new-group ranks straight from the parents (out[m] = the group count)
-void exclusive_scan_roots(const uint32_t *par, uint32_t m, uint32_t *out, ScanScratch ss,
-                          hipStream_t st, uint32_t *total = nullptr);
+// The new-group ranks straight from the parents: rank(k) = number of roots
+// (par[j] == j) among j < k, left in each root's own parent word as
+// ROOT_FLAG | rank (non-roots keep their parents; no output array), the
+// group count into *total.  Bit 31 is free: the record pipeline
+// takes fewer than 2^30 rows (record_eligible, rk_api.hip), so every index
+// and every rank is below 2^30.
+constexpr uint32_t ROOT_FLAG = 0x80000000u;
+void scan_root_ranks(uint32_t *par, uint32_t m, ScanScratch ss, hipStream_t st, uint32_t *total);
 
 // Launch-level HIP-event timing of the pipeline's kernels, active only while a
 // context profiles (rk_set_profiling): rk_classify_device points g_ktimer at
@@ -470,12 +474,12 @@ void nw_fill_y(const uint32_t *ent, const uint32_t *bits, uint8_t *state, uint32
                hipStream_t st);
 void nw_assign(const uint32_t *par, const uint32_t *newrank, uint32_t *gidp, uint32_t m,
                const NwDigits &e, uint32_t *ehist, hipStream_t st);
-// the roots and gids in one pass after exclusive_scan_roots (list: m words of
+// the roots and gids in one pass after scan_root_ranks (the roots' parent
+// words hold ROOT_FLAG | rank, ctrl[32] the group count; list: m words of
 // scratch; ctrl[12] its count (zero on entry), ctrl[13] = 1 when a chain stayed open after
 // 4128 steps, ctrl[0] |= ERRB_INTERNAL on a parent after its child)
-void nw_assign_jump(uint32_t *par, const uint32_t *newrank, uint32_t *gidp, uint32_t m,
-                    const NwDigits &e, uint32_t *ehist, uint32_t *list, uint32_t *ctrl,
-                    hipStream_t st);
+void nw_assign_jump(uint32_t *par, uint32_t *gidp, uint32_t m, const NwDigits &e,
+                    uint32_t *ehist, uint32_t *list, uint32_t *ctrl, hipStream_t st);
 void nw_member_sort(const uint4 *erec, const uint32_t *gidp, uint4 *t0, uint4 *t1, uint32_t m,
                     const NwDigits &e, const uint32_t *ehist, uint32_t *status, uint32_t *sgid,
                     uint64_t *key, uint32_t *tag, uint32_t *mrow, bool narrow_keys,

@@ -1226,41 +1226,47 @@ __global__ void __launch_bounds__(256) k_nw_assign(const uint32_t *__restrict__ 
 }
 
 // The roots and the gids in one pass (the new-group ranks already scanned from
-// the parents' root flags, exclusive_scan_roots): each member chases its
-// parent chain up to `steps` steps, writes the root back as its parent (so
-// later chases are short), and its gid = newrank[root] with the member sort's
-// digit histograms; a longer chain is listed for k_nw_assign_rest.  Replaces
-// k_jump's first round + the flag scan + k_nw_assign (their flag array
-// written and read, the parents read twice).
+// the parents' root flags, scan_root_ranks: a root's parent word holds
+// ROOT_FLAG | rank): each member chases its parent chain up to `steps` steps
+// until it loads a flagged word, whose low bits are its gid -- no rank array,
+// no load after the chase -- and feeds the member sort's digit histograms; a
+// longer chain is listed for k_nw_assign_rest.  Replaces k_jump's first round
+// + the flag scan + k_nw_assign (their flag array written and read, the
+// parents read twice).
 //
-// Every gid written is below G = newrank[m], whatever happens: each of the G
-// roots (par[r] == r, never rewritten) takes its own rank, so no group is
-// empty and the member sort and the group sort downstream stay in bounds even
-// when a chain is left open (*open: the caller then classifies again the
-// round-by-round way) or a parent is corrupt (ERRB_INTERNAL: the call fails).
+// Every gid written is below G (ctrl[32]), whatever the parents hold: each of
+// the G roots takes its own rank from its own word, so no group is empty and
+// the member sort and the group sort downstream stay in bounds even when a
+// chain is left open (*open: the caller then classifies again the
+// round-by-round way), a parent is corrupt (ERRB_INTERNAL: the call fails) or
+// a flagged word is stale (an earlier call's, in a slot no sweep rewrote: its
+// rank is clamped like any other).
 
-// chase from `a` at most `steps` steps; stops at a root (true) or at a parent
-// not before its child (error bit; `a` is then taken as the end)
-__device__ __forceinline__ bool chase_root(const uint32_t *par, uint32_t &a, int steps,
-                                           uint32_t *err) {
-  for (int step = 0; step < steps; ++step) {
+// chase from `a` at most `steps` steps.  True: the chain ended, *g its gid
+// before the clamp -- the rank in a flagged word, or (error bit set) the index
+// whose parent was not before it.  False: still open at `a`.  (A flagged word
+// compares above every index: the flag is tested first.)
+__device__ __forceinline__ bool chase_rank(const uint32_t *par, uint32_t &a, int steps,
+                                           uint32_t *err, uint32_t *g) {
+  for (int step = 0; step <= steps; ++step) {
     const uint32_t b = par[a];
-    if (b == a) return true;
-    if (b > a) {  // parents are always earlier
-      atomicOr(err, ERRB_INTERNAL);
+    if (b & ROOT_FLAG) {
+      *g = b & ~ROOT_FLAG;
       return true;
     }
+    if (b >= a) {  // parents are always earlier, and every root is flagged
+      atomicOr(err, ERRB_INTERNAL);
+      *g = a;
+      return true;
+    }
+    if (step == steps) break;  // (the last load only looks for the flag)
     a = b;
   }
-  return par[a] == a;
-}
-__device__ __forceinline__ uint32_t gid_of(const uint32_t *newrank, uint32_t a, uint32_t G) {
-  const uint32_t g = newrank[a];
-  return g < G ? g : G - 1u;  // (only a corrupt parent or an open chain needs the clamp)
+  return false;
 }
 
 __global__ void __launch_bounds__(256) k_nw_assign_jump(uint32_t *__restrict__ par,
-                                                        const uint32_t *__restrict__ newrank,
+                                                        const uint32_t *__restrict__ gcount,
                                                         uint32_t *__restrict__ gidp, uint32_t m,
                                                         Digits D, uint32_t *__restrict__ ghist,
                                                         uint32_t *__restrict__ list,
@@ -1270,25 +1276,31 @@ __global__ void __launch_bounds__(256) k_nw_assign_jump(uint32_t *__restrict__ p
   hist_init(L);
   __syncthreads();
   const uint32_t lane = threadIdx.x & 63;
-  const uint32_t G = newrank[m];  // >= 1: the first fragment always opens a group
+  const uint32_t G = max(*gcount, 1u);  // (>= 1 anyway: the first fragment always opens a group)
   for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k - lane < m;
        k += gridDim.x * blockDim.x) {
     bool open = false;
     if (k < m) {
       const uint32_t a0 = par[k];
-      uint32_t a = a0;
-      bool done;
-      if (a0 > k) {  // corrupt: taken as its own root
+      uint32_t g;
+      bool done = true;
+      if (a0 & ROOT_FLAG) {  // a root: its rank is here
+        g = a0 & ~ROOT_FLAG;
+      } else if (a0 >= k) {  // corrupt (an unflagged k is no root either)
         atomicOr(err, ERRB_INTERNAL);
-        a = k;
-        done = true;
+        g = k;
       } else {
-        done = chase_root(par, a, steps, err);
-        if (a != a0) par[k] = a;
+        uint32_t a = a0;
+        done = chase_rank(par, a, steps, err, &g);
+        // the rank itself back as k's parent word: a chain that runs through
+        // k ends here without a load of the root (a reader sees the old
+        // earlier index or this final word: an aligned 32-bit store)
+        if (done) par[k] = ROOT_FLAG | g;
+        else if (a != a0) par[k] = a;
       }
       open = !done;
       if (done) {
-        const uint32_t g = gid_of(newrank, a, G);
+        g = g < G ? g : G - 1u;  // (only a corrupt parent or a stale word needs the clamp)
         gidp[k] = g;
         hist_add(L, D, g);
       }
@@ -1307,17 +1319,25 @@ __global__ void __launch_bounds__(256) k_nw_assign_jump(uint32_t *__restrict__ p
 
 // the listed chains, followed further (up to `steps` more); a chain still open
 // sets *open and takes a clamped gid (the caller classifies again)
-__global__ void k_nw_assign_rest(uint32_t *par, const uint32_t *newrank, uint32_t *gidp,
-                                 uint32_t m, Digits D, uint32_t *ghist, const uint32_t *list,
+__global__ void k_nw_assign_rest(uint32_t *par, const uint32_t *gcount, uint32_t *gidp,
+                                 Digits D, uint32_t *ghist, const uint32_t *list,
                                  const uint32_t *count, uint32_t *open, uint32_t *err,
                                  int steps) {
-  const uint32_t n = *count, G = newrank[m];
+  const uint32_t n = *count, G = max(*gcount, 1u);
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
     const uint32_t k = list[i];
-    uint32_t a = par[k];
-    if (!chase_root(par, a, steps, err)) *open = 1u;
-    par[k] = a;
-    const uint32_t g = gid_of(newrank, a, G);
+    uint32_t a = par[k], g;  // (unflagged and before k: the first pass left it so)
+    if (a >= k) {            // (so never taken; no index is followed unchecked)
+      atomicOr(err, ERRB_INTERNAL);
+      g = k;
+    } else {
+      if (!chase_rank(par, a, steps, err, &g)) {
+        *open = 1u;
+        g = a;
+      }
+      par[k] = a;
+    }
+    g = g < G ? g : G - 1u;
     gidp[k] = g;
     for (int p = 0; p < D.passes; ++p) atomicAdd(&ghist[p * 1024 + D.digit(p, g)], 1u);
   }
@@ -2205,9 +2225,8 @@ void nw_fill_y(const uint32_t *ent, const uint32_t *bits, uint8_t *state, uint32
   kt_end(st, KID_NW_FILLY, 5.0 * m);
 }
 
-void nw_assign_jump(uint32_t *par, const uint32_t *newrank, uint32_t *gidp, uint32_t m,
-                    const NwDigits &e, uint32_t *ehist, uint32_t *list, uint32_t *ctrl,
-                    hipStream_t st) {
+void nw_assign_jump(uint32_t *par, uint32_t *gidp, uint32_t m, const NwDigits &e,
+                    uint32_t *ehist, uint32_t *list, uint32_t *ctrl, hipStream_t st) {
   if (!m) return;
   // the step budgets (RK_ROOTS_STEPS / RK_ROOTS_REST_STEPS: test hooks for the
   // listed chains and the round-by-round fallback)
@@ -2220,12 +2239,12 @@ void nw_assign_jump(uint32_t *par, const uint32_t *newrank, uint32_t *gidp, uint
     return e ? std::max(1, atoi(e)) : 4096;
   }();
   kt_begin(st, KID_NW_ASSIGN);
-  k_nw_assign_jump<<<grid_for(m, 256, 2048), 256, 0, st>>>(par, newrank, gidp, m, to_digits(e),
+  k_nw_assign_jump<<<grid_for(m, 256, 2048), 256, 0, st>>>(par, ctrl + 32, gidp, m, to_digits(e),
                                                            ehist, list, ctrl + 12, ctrl, steps1);
-  // parent, root (+ its parent), parent back, root's rank, gid
-  kt_end(st, KID_NW_ASSIGN, 20.0 * m);
-  k_nw_assign_rest<<<256, 256, 0, st>>>(par, newrank, gidp, m, to_digits(e), ehist, list,
-                                        ctrl + 12, ctrl + 13, ctrl, steps2);
+  // parent, the chain's flagged word, the rank back as the parent, gid
+  kt_end(st, KID_NW_ASSIGN, 16.0 * m);
+  k_nw_assign_rest<<<256, 256, 0, st>>>(par, ctrl + 32, gidp, to_digits(e), ehist, list, ctrl + 12,
+                                        ctrl + 13, ctrl, steps2);
 }
 
 void nw_assign(const uint32_t *par, const uint32_t *newrank, uint32_t *gidp, uint32_t m,

@@ -133,6 +133,40 @@ __global__ void __launch_bounds__(SCAN_THREADS) k_scan_tiles(const In in, uint32
   if (clear0 && blockIdx.x == 0 && threadIdx.x == 0) *clear0 = 0u;
 }
 
+// The root flags' scan with each root's rank left in its own parent word
+// (ROOT_FLAG | rank) instead of an output array: a chase that loads a root's
+// word has its gid.  Non-roots keep their parents.  A tile reads its 4096
+// words before it writes them and no tile reads another's; the reduce launch
+// over the same words has finished before this one starts.  G (the scan's
+// word at position m) goes to *total.
+__global__ void __launch_bounds__(SCAN_THREADS) k_scan_root_ranks(uint32_t *par, size_t m,
+                                                                  const uint32_t *prefix,
+                                                                  uint32_t *total) {
+  const size_t tile = (size_t)blockIdx.x * SCAN_TILE;
+  uint32_t carry = prefix ? prefix[blockIdx.x] : 0u;
+  uint4 p[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) p[r] = load4(par, tile + (size_t)r * SCAN_ROW + threadIdx.x * 4, m);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const size_t base = tile + (size_t)r * SCAN_ROW + threadIdx.x * 4;
+    const uint32_t fx = base + 0 < m && p[r].x == base + 0, fy = base + 1 < m && p[r].y == base + 1,
+                   fz = base + 2 < m && p[r].z == base + 2, fw = base + 3 < m && p[r].w == base + 3;
+    uint32_t tot;
+    const uint32_t ex = block_excl_scan(fx + fy + fz + fw, &tot) + carry;
+    const uint32_t ey = ex + fx, ez = ey + fy, ew = ez + fz;
+    if (fx | fy | fz | fw)  // (only a quad with a root changes)
+      store4(par, base, m,
+             make_uint4(fx ? ROOT_FLAG | ex : p[r].x, fy ? ROOT_FLAG | ey : p[r].y,
+                        fz ? ROOT_FLAG | ez : p[r].z, fw ? ROOT_FLAG | ew : p[r].w));
+    if (base <= m && m < base + 4) {  // the exclusive word at position m: every root
+      const uint32_t j = (uint32_t)(m - base);
+      *total = j == 0 ? ex : j == 1 ? ey : j == 2 ? ez : ew;
+    }
+    carry += tot;
+  }
+}
+
 // Single pass (one launch instead of three, the input read once): tile b
 // (= blockIdx.x) scans its 4096 words, publishes its aggregate, finds its
 // prefix by a decoupled look-back over the tiles before it and publishes its
@@ -280,9 +314,21 @@ void exclusive_scan_u32_clear0(uint32_t *in, uint32_t *out, size_t n, ScanScratc
   scan_any(WordsIn{in}, out, n, ss, st, nullptr, in);
 }
 
-void exclusive_scan_roots(const uint32_t *par, uint32_t m, uint32_t *out, ScanScratch ss,
-                          hipStream_t st, uint32_t *total) {
-  scan_any(RootsIn{par, m}, out, (size_t)m + 1, ss, st, total);
+// (always reduce-then-scan: the tiles' sums are complete before any parent
+// word changes, whatever order the tiles of the last launch run in)
+void scan_root_ranks(uint32_t *par, uint32_t m, ScanScratch ss, hipStream_t st, uint32_t *total) {
+  const size_t n = (size_t)m + 1;
+  if (n <= (size_t)SCAN_TILE) {
+    k_scan_root_ranks<<<1, SCAN_THREADS, 0, st>>>(par, m, nullptr, total);
+    return;
+  }
+  const size_t nb = (n + SCAN_TILE - 1) / SCAN_TILE;
+  uint32_t *sums = ss.block_sums;
+  const size_t stride = (nb + 4) & ~(size_t)3;
+  ScanScratch rest{ss.block_sums + stride, ss.cap - stride};
+  k_reduce_tiles<<<(unsigned)nb, SCAN_THREADS, 0, st>>>(RootsIn{par, m}, n, sums);
+  scan_any(WordsIn{sums}, sums, nb, rest, st);
+  k_scan_root_ranks<<<(unsigned)nb, SCAN_THREADS, 0, st>>>(par, m, sums, total);
 }
 
 }  // namespace rk

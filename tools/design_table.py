@@ -25,7 +25,7 @@ JOBS = [
     ("k_nw_x_bits", "X hits as a bitmask by processing index (ballots over the X states at each fragment's X position), read in order by the first Y pass", "5"),
     ("k_nw_fill_y", "Y states from the bitmask for later ratio pairs (X hits sit in the Y lists)", "5"),
     ("k_jump", "(RK_ROOTS_FUSED=0 only) chase parent chains to the root, round by round", "16"),
-    ("k_nw_assign", "`k_nw_assign_jump`: after the scan of the parents' root flags, each member chases its chain (up to 32 links; longer ones listed for `k_nw_assign_rest`), writes the root back as its parent and takes gid = the root's rank, with the member-sort histograms", "20"),
+    ("k_nw_assign", "`k_nw_assign_jump`: after the scan that leaves each root's rank in its own parent word (bit 31 set), each member chases its chain (up to 32 links; longer ones listed for `k_nw_assign_rest`) to the first flagged word, whose low bits are its gid, stores that flagged rank back as its parent and feeds the member-sort histograms", "16"),
     ("k_group_offsets", "`k_group_offsets_emit`: group bounds, and from them alone every position's repeat flag and the singletons' rows (four positions per thread, the flags as one word)", "5 + 8 per singleton"),
     ("k_sort_small", "groups of 2..16 members (insertion sort == stable rank): 16 lanes per group from the tier list, width-16 shuffles; singletons are not touched (second stream); a ranked member's file row goes to the output", "16 per member"),
     ("k_sort_groups_reg", "17..64 members in registers (17..32: two groups per wavefront, second stream; 33..64: main stream, after its LDS tiers); rows stored, as above", "16 per member"),
