@@ -361,6 +361,47 @@ int rk_db_load_soa(const char *path, rk_db **db);
 int rk_db_view(const rk_db *db, rk_frags_soa *soa, uint64_t *len_x_hdr, uint64_t *len_y_hdr,
                uint64_t *total_hdr);
 
+/* ---- device ingress: the same FragmentsDatabase, parsed on the GPU ------
+ *
+ * rk_db_load_csv_device reads the 16 header lines on the host and sends the
+ * body bytes to the device, where one lane per line applies the acceptance
+ * rules of FragmentsDatabase.cpp:17-101; lines whose similarity field needs
+ * strtof (or that are longer than rk_csv_max_line() bytes) are parsed by the
+ * host's own parser and patched in.  The resulting rk_db is the one
+ * rk_db_load_csv builds from the same file, for every consumer (rk_db_view,
+ * rk_db_write_csv, rk_saver_*, rk_db_save_soa).  Bodies larger than
+ * RK_CSV_WINDOW bytes (environment, read on every call, default 8 GiB) go
+ * through the device in windows cut at line boundaries.
+ * RK_E_IO / RK_E_COUNT as rk_db_load_csv (FragmentsDatabase.cpp:17-101);
+ * RK_E_ARG for null arguments; RK_E_NOMEM / RK_E_HIP on device failures
+ * (rk_last_error). */
+enum { RK_DB_KEEP_DEVICE = 1 };  /* keep x_start, y_start, length, strand in HBM */
+int rk_db_load_csv_device(rk_ctx *ctx, const char *path, uint32_t flags, rk_db **db);
+/* device SoA of a database loaded with RK_DB_KEEP_DEVICE (FragmentsDatabase.cpp:17-101's
+   columns, resident), valid until rk_db_free; RK_E_ARG for any other database */
+int rk_db_device_view(const rk_db *db, rk_frags_soa *soa_dev);
+/* Classify a database loaded with RK_DB_KEEP_DEVICE from its resident columns:
+ * rk_classify_device_pairs on the device view (no second upload), then the
+ * results downloaded into the caller's HOST arrays, as rk_classify_pairs fills
+ * them.  The header values come from the database (FragmentsDatabase.cpp:17-101);
+ * len_ratio[i] / pos_ratio[i] / out[i] belong to pair i. */
+int rk_classify_db_pairs(rk_ctx *ctx, const rk_db *db, const double *len_ratio,
+                         const double *pos_ratio, uint32_t npairs, rk_result *out);
+/* The last rk_db_load_csv_device on a context (FragmentsDatabase.cpp:17-101's
+ * work, leg by leg): body bytes, body lines, accepted rows, lines the host
+ * parsed, device windows; host wall time of the body upload, HIP-event time
+ * of the ingress kernels, host wall time of the host-line fix-up and of the
+ * column download, and of the whole call. */
+typedef struct {
+  uint64_t body_bytes, lines, accepted, host_lines;
+  uint32_t windows;
+  double h2d_ms, device_ms, host_fix_ms, d2h_ms, total_ms;
+} rk_ingress_stats;
+int rk_get_ingress_stats(const rk_ctx *ctx, rk_ingress_stats *st);
+/* The longest line a device lane parses, and the line index's tile, in bytes. */
+uint32_t rk_csv_max_line(void);
+uint32_t rk_csv_tile(void);
+
 /* ---- host egress: save_all_frag_pairs + SaverQueue ------------------- */
 
 /* Write the reference's output CSV (commonFunctions.cpp:101-146). */

@@ -10,7 +10,9 @@ Mapping to the reference (``/root/reference/src``):
 =====================================  ============================================
 reference                              here
 =====================================  ============================================
-``FragmentsDatabase(ifstream&, ...)``  :class:`FragmentsDatabase` (``rk_db_load_csv``)
+``FragmentsDatabase(ifstream&, ...)``  :class:`FragmentsDatabase` (``rk_db_load_csv``;
+                                       with ``ctx=`` parsed on the GPU,
+                                       ``rk_db_load_csv_device``)
 ``generate_fragment_groups`` +         :meth:`Context.classify` /
 ``generate_diagonal_func`` +           :meth:`Context.classify_device`
 ``sort_groups`` + repeat flag          (``rk_classify`` / ``rk_classify_device``)
@@ -52,7 +54,11 @@ EXPORTS = (
     "rk_shard_copy_result", "rk_comm_create_local", "rk_classify_sharded_host",
     "rk_comm_abandon", "rk_set_pipeline",
     "rk_classify_batch", "rk_classify_device_batch", "rk_batch_layout", "rk_get_batch_stats",
+    "rk_db_load_csv_device", "rk_db_device_view", "rk_classify_db_pairs", "rk_get_ingress_stats",
 )
+# declared too, returning uint32_t (sizes the device CSV parser was built with)
+EXPORTS_U32 = ("rk_csv_max_line", "rk_csv_tile")
+RK_DB_KEEP_DEVICE = 1
 
 
 class RkError(RuntimeError):
@@ -110,6 +116,14 @@ class BatchResult(ctypes.Structure):
 class BatchStats(ctypes.Structure):
     _fields_ = [("sub_batches", ctypes.c_uint32), ("looped_sets", ctypes.c_uint32),
                 ("batched_sets", ctypes.c_uint32), ("device_ms", ctypes.c_double)]
+
+
+class IngressStats(ctypes.Structure):
+    _fields_ = [("body_bytes", ctypes.c_uint64), ("lines", ctypes.c_uint64),
+                ("accepted", ctypes.c_uint64), ("host_lines", ctypes.c_uint64),
+                ("windows", ctypes.c_uint32), ("h2d_ms", ctypes.c_double),
+                ("device_ms", ctypes.c_double), ("host_fix_ms", ctypes.c_double),
+                ("d2h_ms", ctypes.c_double), ("total_ms", ctypes.c_double)]
 
 
 ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
@@ -237,6 +251,15 @@ def load_library() -> ctypes.CDLL:
                                                     ctypes.POINTER(BatchResult)]),
         "rk_batch_layout": (ctypes.c_int, [ctypes.c_uint32, vp, vp, vp, vp]),
         "rk_get_batch_stats": (ctypes.c_int, [vp, ctypes.POINTER(BatchStats)]),
+        "rk_db_load_csv_device": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.c_uint32,
+                                                 ctypes.POINTER(vp)]),
+        "rk_db_device_view": (ctypes.c_int, [vp, ctypes.POINTER(FragsSoA)]),
+        "rk_classify_db_pairs": (ctypes.c_int, [vp, vp, ctypes.POINTER(ctypes.c_double),
+                                                ctypes.POINTER(ctypes.c_double), ctypes.c_uint32,
+                                                ctypes.POINTER(Result)]),
+        "rk_get_ingress_stats": (ctypes.c_int, [vp, ctypes.POINTER(IngressStats)]),
+        "rk_csv_max_line": (ctypes.c_uint32, []),
+        "rk_csv_tile": (ctypes.c_uint32, []),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -312,12 +335,28 @@ class ClassifyResult:
 class FragmentsDatabase:
     """Parsed fragment CSV (FragmentsDatabase.cpp:17-101 acceptance rules)."""
 
-    def __init__(self, path: str, soa: bool = False):
+    def __init__(self, path: str, soa: bool = False, ctx: "Context | None" = None,
+                 keep_device: bool = False):
         """path: the fragment CSV, or with soa=True a binary SoA cache written by
-        save_soa (the parsed columns: no parse at all)."""
+        save_soa (the parsed columns: no parse at all).  With ctx the CSV is
+        parsed on that context's GPU (rk_db_load_csv_device); keep_device=True
+        also keeps the four classification columns in HBM (device_view,
+        Context.classify_db)."""
         lib = load_library()
         h = ctypes.c_void_p()
-        rc = (lib.rk_db_load_soa if soa else lib.rk_db_load_csv)(path.encode(), ctypes.byref(h))
+        if ctx is None and keep_device:
+            raise ValueError("keep_device=True needs ctx (the device parse)")
+        if ctx is not None:
+            if soa:
+                raise ValueError("a SoA cache is not parsed: ctx does not apply")
+            rc = lib.rk_db_load_csv_device(ctx._h, path.encode(),
+                                           RK_DB_KEEP_DEVICE if keep_device else 0,
+                                           ctypes.byref(h))
+            if rc not in (0, -2, -3):
+                raise RkError(rc, ctx.last_error())
+        else:
+            rc = (lib.rk_db_load_soa if soa else lib.rk_db_load_csv)(path.encode(),
+                                                                     ctypes.byref(h))
         if rc == -2:
             raise RkError(rc, f"Could not open input file {path}.")
         if rc == -3:
@@ -353,6 +392,16 @@ class FragmentsDatabase:
         if rc == -2:
             raise RkError(rc, f"Could not write {path}")
         _check(rc)
+
+    def device_view(self) -> dict:
+        """The resident columns of a database loaded with keep_device=True
+        (rk_db_device_view): device addresses of x_start, y_start, length,
+        strand and the row count n, valid until close()."""
+        soa = FragsSoA()
+        _check(load_library().rk_db_device_view(self._h, ctypes.byref(soa)),
+               "the database was not loaded with keep_device=True")
+        return {"x_start": soa.x_start or 0, "y_start": soa.y_start or 0,
+                "length": soa.length or 0, "strand": soa.strand or 0, "n": int(soa.n)}
 
     def getTotalFrags(self) -> int:  # FragmentsDatabase.h:32
         return self.frags.n
@@ -503,6 +552,29 @@ class Context:
             raise RkError(rc, self.last_error())
         k = res.n_out
         return ClassifyResult(gid[:k].copy(), rep[:k].copy(), order[:k].copy(), int(res.n_groups))
+
+    def classify_db(self, db: "FragmentsDatabase", len_ratio: float = 0.3,
+                    pos_ratio: float = 0.3) -> ClassifyResult:
+        """Classify a database loaded with keep_device=True from its resident
+        columns: no upload (rk_classify_db_pairs)."""
+        n = db.frags.n
+        gid = np.empty(n, np.uint32)
+        rep = np.empty(n, np.uint8)
+        order = np.empty(n, np.uint32)
+        res = Result(_ptr(order), _ptr(gid), _ptr(rep), 0, 0)
+        lr, pr = ctypes.c_double(len_ratio), ctypes.c_double(pos_ratio)
+        rc = load_library().rk_classify_db_pairs(self._h, db._h, ctypes.byref(lr),
+                                                 ctypes.byref(pr), 1, ctypes.byref(res))
+        if rc != RK_OK:
+            raise RkError(rc, self.last_error())
+        k = res.n_out
+        return ClassifyResult(gid[:k].copy(), rep[:k].copy(), order[:k].copy(), int(res.n_groups))
+
+    def ingress_stats(self) -> dict:
+        """The last device CSV load on this context (rk_get_ingress_stats)."""
+        s = IngressStats()
+        _check(load_library().rk_get_ingress_stats(self._h, ctypes.byref(s)))
+        return {k: getattr(s, k) for k, _ in IngressStats._fields_}
 
     def classify_into(self, f: Frags, len_x_hdr: int, len_y_hdr: int, len_ratio: float,
                       pos_ratio: float, gid: np.ndarray, rep: np.ndarray,

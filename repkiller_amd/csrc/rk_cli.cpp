@@ -19,7 +19,10 @@
 // on one GPU), --comm rccl|local (collectives: RCCL, or in-process device
 // copies; default rccl, local with --same-device), --save-soa PATH (after the
 // parse, keep the database as a binary SoA cache), --soa (the input is such a
-// cache: no parse at all).
+// cache: no parse at all), --device-parse (the CSV body is
+// parsed on the GPU, rk_db_load_csv_device, and every pair is classified from
+// the columns that stay resident there: no second upload; --timing then adds
+// the ingress legs; not with --soa, --batch or --gpus above 1).
 //
 //   rk_repkiller --batch <list> <len_ratio> <pos_ratio>
 //
@@ -42,7 +45,7 @@
 static void print_help() {
   std::printf("Repkiller (MI355X) v0.9.b-compatible\n");
   std::printf("Usage: ./rk_repkiller [--device N] [--gpus P [--same-device] [--comm rccl|local]] "
-              "[--timing] [--save-soa cache.soa | --soa] <input_file_path> <output_file_path> "
+              "[--timing] [--save-soa cache.soa | --soa | --device-parse] <input_file_path> <output_file_path> "
               "<length_ratio> <position_ratio> [<length_ratio> <position_ratio>]...\n");
   std::printf("       ./rk_repkiller [--device N] --batch <list of input<TAB>output lines> "
               "<length_ratio> <position_ratio>\n");
@@ -215,7 +218,7 @@ static int run_batch(const char *list_path, double lr, double pr, int device) {
 
 int main(int argc, char **argv) {
   int device = 0, gpus = 1;
-  bool timing = false, same_device = false, soa_in = false;
+  bool timing = false, same_device = false, soa_in = false, device_parse = false;
   const char *comm_kind = nullptr, *save_soa = nullptr, *batch_list = nullptr;
   std::vector<const char *> pos;
   for (int i = 1; i < argc; ++i) {
@@ -225,6 +228,7 @@ int main(int argc, char **argv) {
     else if (!std::strcmp(argv[i], "--same-device")) same_device = true;
     else if (!std::strcmp(argv[i], "--timing")) timing = true;
     else if (!std::strcmp(argv[i], "--soa")) soa_in = true;
+    else if (!std::strcmp(argv[i], "--device-parse")) device_parse = true;
     else if (!std::strcmp(argv[i], "--save-soa") && i + 1 < argc) save_soa = argv[++i];
     else if (!std::strcmp(argv[i], "--batch") && i + 1 < argc) batch_list = argv[++i];
     else pos.push_back(argv[i]);
@@ -232,6 +236,11 @@ int main(int argc, char **argv) {
   if (gpus < 1 || gpus > 32 ||
       (comm_kind && std::strcmp(comm_kind, "rccl") && std::strcmp(comm_kind, "local"))) {
     std::fprintf(stderr, "Invalid --gpus / --comm.\n");
+    print_help();
+    return 1;
+  }
+  if (device_parse && (soa_in || batch_list || gpus != 1)) {
+    std::fprintf(stderr, "--device-parse does not combine with --soa, --batch or --gpus.\n");
     print_help();
     return 1;
   }
@@ -282,7 +291,21 @@ int main(int argc, char **argv) {
   std::fflush(stdout);
   double t0 = now_s();
   rk_db *db = nullptr;
-  int rc = soa_in ? rk_db_load_soa(pos[0], &db) : rk_db_load_csv(pos[0], &db);
+  rk_ctx *ctx = nullptr;
+  int rc;
+  if (device_parse) {
+    rc = rk_create(&ctx, device);
+    if (rc) {
+      std::fprintf(stderr, "no usable gfx950 device %d (%d)\n", device, rc);
+      return 1;
+    }
+    rc = rk_db_load_csv_device(ctx, pos[0], RK_DB_KEEP_DEVICE, &db);
+    if (rc && rc != RK_E_IO && rc != RK_E_COUNT)
+      std::fprintf(stderr, "device parse: %s\n", rk_last_error(ctx));
+    if (rc) rk_destroy(ctx);
+  } else {
+    rc = soa_in ? rk_db_load_soa(pos[0], &db) : rk_db_load_csv(pos[0], &db);
+  }
   if (rc == RK_E_ARG && soa_in) {
     std::fprintf(stderr, "%s is not a complete SoA cache file.\n", pos[0]);
     return 1;
@@ -301,6 +324,7 @@ int main(int argc, char **argv) {
   }
   if (save_soa && (rc = rk_db_save_soa(db, save_soa))) {
     std::fprintf(stderr, "writing the SoA cache %s failed (%d)\n", save_soa, rc);
+    rk_destroy(ctx);
     rk_db_free(db);
     return 1;
   }
@@ -309,8 +333,7 @@ int main(int argc, char **argv) {
   uint64_t lx, ly, total;
   rk_db_view(db, &soa, &lx, &ly, &total);
 
-  rk_ctx *ctx = nullptr;
-  if (gpus == 1) {
+  if (gpus == 1 && !ctx) {
     rc = rk_create(&ctx, device);
     if (rc) {
       std::fprintf(stderr, "no usable gfx950 device %d (%d)\n", device, rc);
@@ -334,7 +357,12 @@ int main(int argc, char **argv) {
   }
   double a = now_s();
   std::string err;
-  if (gpus == 1) {
+  if (device_parse) {
+    std::vector<double> lrs(q), prs(q);
+    for (size_t i = 0; i < q; ++i) lrs[i] = params[i].first, prs[i] = params[i].second;
+    rc = rk_classify_db_pairs(ctx, db, lrs.data(), prs.data(), (uint32_t)q, rs.data());
+    if (rc) err = rk_last_error(ctx);
+  } else if (gpus == 1) {
     rc = rk_classify_pairs(ctx, &soa, ps.data(), (uint32_t)q, rs.data());
     if (rc) err = rk_last_error(ctx);
   } else {
@@ -355,7 +383,17 @@ int main(int argc, char **argv) {
   double t2 = now_s();
   rc = rk_saver_stop(sq);
   double t3 = now_s();
+  rk_ingress_stats ing{};
+  if (device_parse) rk_get_ingress_stats(ctx, &ing);
   rk_destroy(ctx);
+  if (timing && device_parse)
+    std::fprintf(stderr,
+                 "{\"ingress\": {\"body_bytes\": %llu, \"lines\": %llu, \"accepted\": %llu, "
+                 "\"host_lines\": %llu, \"windows\": %u, \"h2d_ms\": %.3f, \"device_ms\": %.3f, "
+                 "\"host_fix_ms\": %.3f, \"d2h_ms\": %.3f, \"total_ms\": %.3f}}\n",
+                 (unsigned long long)ing.body_bytes, (unsigned long long)ing.lines,
+                 (unsigned long long)ing.accepted, (unsigned long long)ing.host_lines, ing.windows,
+                 ing.h2d_ms, ing.device_ms, ing.host_fix_ms, ing.d2h_ms, ing.total_ms);
   if (timing)
     std::fprintf(stderr,
                  "{\"frags\": %llu, \"pairs\": %zu, \"load_s\": %.6f, \"classify_s\": %.6f, "

@@ -59,6 +59,7 @@ struct rk_ctx {
   // non-null only while a batch's combined set is being classified
   const rk::BatchTables *batch_tables = nullptr;
   rk_batch_stats batch_stats{};
+  rk_ingress_stats ingress{};  // the last rk_db_load_csv_device (rk_csv.hip)
   // the sharded driver's fast path (rk_shard_fast.h): its all-gather messages
   // (pinned, every rank's), the stage fingerprints of the last call that
   // completed on it (a stage whose gathered counts match needs no agreement

@@ -1,0 +1,40 @@
+// rk_db.h -- the parsed database behind rk_db_*, shared by the host ingress
+// (rk_host.cpp, built without HIP) and the device ingress (rk_csv.hip).  Not
+// part of the public ABI.
+#pragma once
+#include <cstdint>
+#include <string>
+#include <vector>
+
+struct rk_db {
+  std::vector<uint64_t> x_start, y_start, x_end, y_end, length, score, ident;
+  std::vector<float> similarity;
+  std::vector<uint8_t> strand;
+  std::string header;
+  uint64_t len_x_hdr = 0, len_y_hdr = 0, total_hdr = 0;
+  // rk_db_load_csv_device with RK_DB_KEEP_DEVICE: x_start, y_start, length and
+  // strand also stay in HBM (one allocation the database owns).  rk_host.cpp
+  // cannot call HIP, so the device side leaves the function that frees it.
+  void *dev_block = nullptr;
+  const uint64_t *dev_x = nullptr, *dev_y = nullptr, *dev_len = nullptr;
+  const uint8_t *dev_strand = nullptr;
+  int dev_device = -1;
+  void (*dev_free)(void *block, int device) = nullptr;
+};
+
+namespace rk {
+
+struct DbRow {
+  uint64_t xs, ys, xe, ye, len, score, ident;
+  float sim;
+  uint8_t strand;
+};
+
+// rk_host.cpp: one body line -> row, or false where readFragment returns false
+bool db_parse_line(const char *b, const char *e, DbRow *r);
+// rk_host.cpp: the 16 header lines of the file [p, end) into db->header and the
+// three header numbers (std::getline semantics); returns where the body starts,
+// *eof set when the file ended inside the header
+const char *db_read_header(rk_db *db, const char *p, const char *end, bool *eof);
+
+}  // namespace rk

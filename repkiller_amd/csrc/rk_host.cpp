@@ -46,15 +46,8 @@
 #include <vector>
 
 #include "repkiller_amd.h"
+#include "rk_db.h"
 #include "rk_format.h"
-
-struct rk_db {
-  std::vector<uint64_t> x_start, y_start, x_end, y_end, length, score, ident;
-  std::vector<float> similarity;
-  std::vector<uint8_t> strand;
-  std::string header;
-  uint64_t len_x_hdr = 0, len_y_hdr = 0, total_hdr = 0;
-};
 
 namespace {
 
@@ -121,11 +114,7 @@ uint64_t float_to_u64_x86(float x) {
 
 // ------------------------------------------------------------------ lines --
 
-struct Row {
-  uint64_t xs, ys, xe, ye, len, score, ident;
-  float sim;
-  uint8_t strand;
-};
+using Row = rk::DbRow;
 
 // One body line -> Row, or false if readFragment would return false.
 bool parse_line(const char *b, const char *e, Row *r) {
@@ -186,26 +175,10 @@ struct Mapped {
 
 }  // namespace
 
-extern "C" int rk_db_load_csv(const char *path, rk_db **out) {
-  if (!path || !out) return RK_E_ARG;
-  *out = nullptr;
-  Mapped m;
-  m.fd = open(path, O_RDONLY);
-  if (m.fd < 0) return RK_E_IO;
-  struct stat st;
-  if (fstat(m.fd, &st) != 0) return RK_E_IO;
-  m.n = (size_t)st.st_size;
-  if (m.n) {
-    void *q = mmap(nullptr, m.n, PROT_READ, MAP_PRIVATE, m.fd, 0);
-    if (q == MAP_FAILED) return RK_E_IO;
-    m.p = (const char *)q;
-    madvise(q, m.n, MADV_SEQUENTIAL);
-  }
-  auto db = new (std::nothrow) rk_db;
-  if (!db) return RK_E_NOMEM;
+bool rk::db_parse_line(const char *b, const char *e, DbRow *r) { return parse_line(b, e, r); }
 
-  // ---- header: 16 std::getline calls on the file stream
-  const char *p = m.p, *end = m.p + m.n;
+// 16 std::getline calls on the file stream
+const char *rk::db_read_header(rk_db *db, const char *p, const char *end, bool *eof_out) {
   bool eof = false;
   const char *lb = p, *le = p;  // current `line` contents
   for (int k = 1; k <= 16; ++k) {
@@ -226,6 +199,32 @@ extern "C" int rk_db_load_csv(const char *path, rk_db **out) {
     if (k == 8) db->len_y_hdr = header_number(lb, le);
     if (k == 13) db->total_hdr = header_number(lb, le);
   }
+  *eof_out = eof;
+  return p;
+}
+
+extern "C" int rk_db_load_csv(const char *path, rk_db **out) {
+  if (!path || !out) return RK_E_ARG;
+  *out = nullptr;
+  Mapped m;
+  m.fd = open(path, O_RDONLY);
+  if (m.fd < 0) return RK_E_IO;
+  struct stat st;
+  if (fstat(m.fd, &st) != 0) return RK_E_IO;
+  m.n = (size_t)st.st_size;
+  if (m.n) {
+    void *q = mmap(nullptr, m.n, PROT_READ, MAP_PRIVATE, m.fd, 0);
+    if (q == MAP_FAILED) return RK_E_IO;
+    m.p = (const char *)q;
+    madvise(q, m.n, MADV_SEQUENTIAL);
+  }
+  auto db = new (std::nothrow) rk_db;
+  if (!db) return RK_E_NOMEM;
+
+  // ---- header
+  const char *end = m.p + m.n;
+  bool eof = false;
+  const char *p = rk::db_read_header(db, m.p, end, &eof);
 
   // ---- body: line-aligned chunks parsed in parallel, concatenated in order
   if (!eof && p < end) {
@@ -443,7 +442,20 @@ extern "C" int rk_db_load_soa(const char *path, rk_db **out) {
   return RK_OK;
 }
 
-extern "C" void rk_db_free(rk_db *db) { delete db; }
+extern "C" void rk_db_free(rk_db *db) {
+  if (db && db->dev_block && db->dev_free) db->dev_free(db->dev_block, db->dev_device);
+  delete db;
+}
+
+extern "C" int rk_db_device_view(const rk_db *db, rk_frags_soa *soa_dev) {
+  if (!db || !soa_dev || !db->dev_free) return RK_E_ARG;
+  soa_dev->x_start = db->dev_x;
+  soa_dev->y_start = db->dev_y;
+  soa_dev->length = db->dev_len;
+  soa_dev->strand = db->dev_strand;
+  soa_dev->n = db->x_start.size();
+  return RK_OK;
+}
 
 extern "C" int rk_db_view(const rk_db *db, rk_frags_soa *soa, uint64_t *len_x_hdr,
                           uint64_t *len_y_hdr, uint64_t *total_hdr) {

@@ -20,6 +20,7 @@ from __future__ import annotations
 
 import argparse
 import filecmp
+import hashlib
 import json
 import os
 import subprocess
@@ -41,6 +42,62 @@ def heartbeat(stop, t0):
         print(f"[io_bench] {time.perf_counter() - t0:.0f} s", file=sys.stderr, flush=True)
 
 
+def sha256_file(path):
+    h = hashlib.sha256()
+    with open(path, "rb") as fh:
+        for blk in iter(lambda: fh.read(1 << 24), b""):
+            h.update(blk)
+    return h.hexdigest()
+
+
+def device_parse_leg(ctx, inp, d, host_csv, reps):
+    """The host route (rk_db_load_csv -> rk_classify -> rk_db_write_csv) and the
+    device-parse route (rk_db_load_csv_device with the columns kept resident ->
+    rk_classify_db_pairs -> rk_db_write_csv) on the same file, alternating,
+    page cache warm for both.  The host route is the yardstick: it is timed
+    here, in the same job on the same box."""
+    want = sha256_file(host_csv)
+    legs = {"host": [], "device": []}
+    for _ in range(reps):
+        for route in ("host", "device"):
+            out_csv = os.path.join(d, f"leg_{route}.csv")
+            t0 = time.perf_counter()
+            if route == "host":
+                db = rk.FragmentsDatabase(inp)
+            else:
+                db = rk.FragmentsDatabase(inp, ctx=ctx, keep_device=True)
+            t1 = time.perf_counter()
+            if route == "host":
+                res = ctx.classify(db.frags, db.len_x_hdr, db.len_y_hdr, 0.3, 0.3)
+            else:
+                res = ctx.classify_db(db, 0.3, 0.3)
+            t2 = time.perf_counter()
+            db.save_all_frag_pairs(out_csv, res)
+            t3 = time.perf_counter()
+            leg = {"load_s": round(t1 - t0, 3), "classify_s": round(t2 - t1, 3),
+                   "save_s": round(t3 - t2, 3), "total_s": round(t3 - t0, 3)}
+            if route == "device":
+                st = ctx.ingress_stats()
+                leg["ingress"] = {k: (round(v, 3) if isinstance(v, float) else v)
+                                  for k, v in st.items()}
+                # the load is synchronous; the resident columns were complete
+                # before the download of the host columns began
+                leg["resident_columns_s"] = round(
+                    (st["h2d_ms"] + st["device_ms"] + st["host_fix_ms"]) / 1e3, 3)
+            leg["same_csv_as_host_route"] = sha256_file(out_csv) == want
+            os.remove(out_csv)
+            db.close()
+            del db, res
+            legs[route].append(leg)
+    summary = {}
+    for route, runs in legs.items():
+        tot = sorted(r["total_s"] for r in runs)
+        summary[route] = {"total_s_median": tot[len(tot) // 2], "total_s_min": tot[0],
+                          "total_s_max": tot[-1],
+                          "load_s_median": sorted(r["load_s"] for r in runs)[len(runs) // 2]}
+    return {"reps": reps, "legs": legs, "summary": summary, "host_csv_sha256": want}
+
+
 def main():
     import threading
     stop = threading.Event()
@@ -49,6 +106,9 @@ def main():
     ap.add_argument("--n", type=int, default=50_000_000)
     ap.add_argument("--genome", type=int, default=3_000_000_000)  # cfg3
     ap.add_argument("--no-ref", action="store_true")
+    ap.add_argument("--device-parse-reps", type=int, default=0,
+                    help="alternate the host route and the device-parse route this many times "
+                         "each on the same file (warm page cache) and record both")
     ap.add_argument("--tmp", default=os.environ.get("TMPDIR", "/tmp"))
     args = ap.parse_args()
     n, L = args.n, args.genome
@@ -105,6 +165,9 @@ def main():
         os.remove(ours2)
         os.remove(cache)
         del db2, res2
+        if args.device_parse_reps > 0:
+            del db, res
+            out["device_parse"] = device_parse_leg(ctx, inp, d, ours, args.device_parse_reps)
         ref = os.path.join(ROOT, "oracle", "_ref", "ref_driver")
         if not args.no_ref and os.path.exists(ref):
             theirs = os.path.join(d, "ref.csv")
