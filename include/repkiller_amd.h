@@ -376,6 +376,9 @@ int rk_db_view(const rk_db *db, rk_frags_soa *soa, uint64_t *len_x_hdr, uint64_t
  * RK_E_ARG for null arguments; RK_E_NOMEM / RK_E_HIP on device failures
  * (rk_last_error). */
 enum { RK_DB_KEEP_DEVICE = 1 };  /* keep x_start, y_start, length, strand in HBM */
+/* all nine columns stay in HBM (61 B per row), for rk_db_write_csv_device; any
+   other flag bit, and bit 1 alone, is RK_E_ARG */
+enum { RK_DB_KEEP_ROWS = 3 };
 int rk_db_load_csv_device(rk_ctx *ctx, const char *path, uint32_t flags, rk_db **db);
 /* device SoA of a database loaded with RK_DB_KEEP_DEVICE (FragmentsDatabase.cpp:17-101's
    columns, resident), valid until rk_db_free; RK_E_ARG for any other database */
@@ -414,6 +417,44 @@ typedef struct rk_saver rk_saver;
 int rk_saver_start(const rk_db *db, rk_saver **sq);
 int rk_saver_add(rk_saver *sq, const char *path, const rk_result *res, uint64_t n);
 int rk_saver_stop(rk_saver *sq); /* drains the queue, joins, frees */
+
+/* ---- device egress: save_all_frag_pairs formatted on the GPU -------------
+ *
+ * rk_db_write_csv_device writes the file rk_db_write_csv writes
+ * (commonFunctions.cpp:101-146), byte for byte, from the nine columns a
+ * database loaded with RK_DB_KEEP_ROWS keeps in HBM: chunks of RK_CSV_OUT_ROWS
+ * output rows (environment, read on every call, clamped to [1, 2^24]) are
+ * formatted by one lane per row, brought down through the pinned staging ring
+ * and written from it.  Rows whose similarity or identity is not a float the
+ * device prints exactly (anything but +0 and [1e-3, 1e6)) are formatted by the
+ * host's own formatter and patched in.  Without RK_RES_DEVICE the result arrays
+ * are host memory and are uploaded first.  rk_classify_db_pairs_to_csv is
+ * rk_classify_db_pairs followed by that save for every pair
+ * (commonFunctions.cpp:131-146's loop over the groups, 101-146 in all) with no
+ * download of the result arrays between the two.
+ * RK_E_ARG: a null argument, an unknown flag bit, a database not loaded with
+ * RK_DB_KEEP_ROWS or resident on another device (rk_last_error), an out_order
+ * entry >= n; RK_E_IO: the path cannot be opened (nothing else is done) or a
+ * write fails (commonFunctions.cpp:101-146). */
+enum { RK_RES_DEVICE = 1 };   /* res->out_order / gid / repval are device pointers */
+int rk_db_write_csv_device(rk_ctx *ctx, const rk_db *db, const char *path,
+                           const rk_result *res, uint32_t flags);
+/* classify from the resident columns and write pair i to paths[i]; the result
+   arrays never leave the device.  n_out / n_groups: nullable HOST arrays, npairs entries */
+int rk_classify_db_pairs_to_csv(rk_ctx *ctx, const rk_db *db, const double *len_ratio,
+                                const double *pos_ratio, uint32_t npairs,
+                                const char *const *paths, uint64_t *n_out, uint64_t *n_groups);
+/* The last rk_db_write_csv_device on a context, or the last pair of a
+ * rk_classify_db_pairs_to_csv (commonFunctions.cpp:101-146's work, leg by leg):
+ * rows and body bytes written, rows the host formatted, chunks; host wall time
+ * of the result upload, HIP-event time of the egress kernels, host wall time of
+ * the host-row fix-up, of the download-and-write leg, and of the whole call. */
+typedef struct {
+  uint64_t rows, bytes, host_rows;
+  uint32_t chunks;
+  double upload_ms, device_ms, host_fix_ms, d2h_write_ms, total_ms;
+} rk_egress_stats;
+int rk_get_egress_stats(const rk_ctx *ctx, rk_egress_stats *st);
 
 /* ---- synthetic inputs --------------------------------- */
 

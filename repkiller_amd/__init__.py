@@ -17,6 +17,8 @@ reference                              here
 ``generate_diagonal_func`` +           :meth:`Context.classify_device`
 ``sort_groups`` + repeat flag          (``rk_classify`` / ``rk_classify_device``)
 ``save_all_frag_pairs``                :meth:`FragmentsDatabase.save_all_frag_pairs`
+                                       (on the GPU: ``save_all_frag_pairs_device``,
+                                       ``rk_db_write_csv_device``)
 ``SaverQueue``                         :class:`SaverQueue` (``rk_saver_*``)
 =====================================  ============================================
 """
@@ -55,10 +57,13 @@ EXPORTS = (
     "rk_comm_abandon", "rk_set_pipeline",
     "rk_classify_batch", "rk_classify_device_batch", "rk_batch_layout", "rk_get_batch_stats",
     "rk_db_load_csv_device", "rk_db_device_view", "rk_classify_db_pairs", "rk_get_ingress_stats",
+    "rk_db_write_csv_device", "rk_classify_db_pairs_to_csv", "rk_get_egress_stats",
 )
 # declared too, returning uint32_t (sizes the device CSV parser was built with)
 EXPORTS_U32 = ("rk_csv_max_line", "rk_csv_tile")
 RK_DB_KEEP_DEVICE = 1
+RK_DB_KEEP_ROWS = 3  # all nine columns resident: the device egress formats from them
+RK_RES_DEVICE = 1    # rk_db_write_csv_device: the result arrays are device pointers
 
 
 class RkError(RuntimeError):
@@ -124,6 +129,14 @@ class IngressStats(ctypes.Structure):
                 ("windows", ctypes.c_uint32), ("h2d_ms", ctypes.c_double),
                 ("device_ms", ctypes.c_double), ("host_fix_ms", ctypes.c_double),
                 ("d2h_ms", ctypes.c_double), ("total_ms", ctypes.c_double)]
+
+
+class EgressStats(ctypes.Structure):
+    _fields_ = [("rows", ctypes.c_uint64), ("bytes", ctypes.c_uint64),
+                ("host_rows", ctypes.c_uint64), ("chunks", ctypes.c_uint32),
+                ("upload_ms", ctypes.c_double), ("device_ms", ctypes.c_double),
+                ("host_fix_ms", ctypes.c_double), ("d2h_write_ms", ctypes.c_double),
+                ("total_ms", ctypes.c_double)]
 
 
 ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
@@ -258,6 +271,14 @@ def load_library() -> ctypes.CDLL:
                                                 ctypes.POINTER(ctypes.c_double), ctypes.c_uint32,
                                                 ctypes.POINTER(Result)]),
         "rk_get_ingress_stats": (ctypes.c_int, [vp, ctypes.POINTER(IngressStats)]),
+        "rk_db_write_csv_device": (ctypes.c_int, [vp, vp, ctypes.c_char_p, ctypes.POINTER(Result),
+                                                  ctypes.c_uint32]),
+        "rk_classify_db_pairs_to_csv": (ctypes.c_int, [vp, vp, ctypes.POINTER(ctypes.c_double),
+                                                       ctypes.POINTER(ctypes.c_double),
+                                                       ctypes.c_uint32,
+                                                       ctypes.POINTER(ctypes.c_char_p), _u64p,
+                                                       _u64p]),
+        "rk_get_egress_stats": (ctypes.c_int, [vp, ctypes.POINTER(EgressStats)]),
         "rk_csv_max_line": (ctypes.c_uint32, []),
         "rk_csv_tile": (ctypes.c_uint32, []),
     }
@@ -336,20 +357,22 @@ class FragmentsDatabase:
     """Parsed fragment CSV (FragmentsDatabase.cpp:17-101 acceptance rules)."""
 
     def __init__(self, path: str, soa: bool = False, ctx: "Context | None" = None,
-                 keep_device: bool = False):
+                 keep_device: bool = False, keep_rows: bool = False):
         """path: the fragment CSV, or with soa=True a binary SoA cache written by
         save_soa (the parsed columns: no parse at all).  With ctx the CSV is
         parsed on that context's GPU (rk_db_load_csv_device); keep_device=True
         also keeps the four classification columns in HBM (device_view,
-        Context.classify_db)."""
+        Context.classify_db); keep_rows=True keeps all nine (RK_DB_KEEP_ROWS:
+        save_all_frag_pairs_device, Context.classify_db_to_csv)."""
         lib = load_library()
         h = ctypes.c_void_p()
-        if ctx is None and keep_device:
-            raise ValueError("keep_device=True needs ctx (the device parse)")
+        if ctx is None and (keep_device or keep_rows):
+            raise ValueError("keep_device / keep_rows need ctx (the device parse)")
         if ctx is not None:
             if soa:
                 raise ValueError("a SoA cache is not parsed: ctx does not apply")
             rc = lib.rk_db_load_csv_device(ctx._h, path.encode(),
+                                           RK_DB_KEEP_ROWS if keep_rows else
                                            RK_DB_KEEP_DEVICE if keep_device else 0,
                                            ctypes.byref(h))
             if rc not in (0, -2, -3):
@@ -416,6 +439,24 @@ class FragmentsDatabase:
         if rc == -2:
             raise RkError(rc, "Could not open output directory " + path)
         _check(rc)
+
+    def save_all_frag_pairs_device(self, ctx: "Context", path: str, res) -> None:
+        """save_all_frag_pairs formatted on the GPU (rk_db_write_csv_device) from
+        the columns a keep_rows=True database keeps resident.  res: a
+        ClassifyResult (host arrays, uploaded first), or a tuple of three device
+        tensors (out_order, gid, repval) whose length is the row count."""
+        if isinstance(res, ClassifyResult):
+            r, flags = res.as_struct(), 0
+        else:
+            order, gid, rep = res
+            r = Result(order.data_ptr(), gid.data_ptr(), rep.data_ptr(), int(order.shape[0]), 0)
+            flags = RK_RES_DEVICE
+        rc = load_library().rk_db_write_csv_device(ctx._h, self._h, path.encode(),
+                                                   ctypes.byref(r), flags)
+        if rc == -2:
+            raise RkError(rc, "Could not open output directory " + path)
+        if rc != RK_OK:
+            raise RkError(rc, ctx.last_error())
 
     def close(self):
         if getattr(self, "_h", None):
@@ -569,6 +610,34 @@ class Context:
             raise RkError(rc, self.last_error())
         k = res.n_out
         return ClassifyResult(gid[:k].copy(), rep[:k].copy(), order[:k].copy(), int(res.n_groups))
+
+    def classify_db_to_csv(self, db: "FragmentsDatabase", pairs, paths) -> list:
+        """Classify a keep_rows=True database at every (len_ratio, pos_ratio) of
+        `pairs` and write pair i to paths[i] from the device: the result arrays
+        never come to the host (rk_classify_db_pairs_to_csv).  Returns
+        [(n_out, n_groups)] per pair."""
+        pairs, paths = list(pairs), list(paths)
+        q = len(pairs)
+        if q != len(paths):
+            raise ValueError("classify_db_to_csv: one path per pair")
+        lr = (ctypes.c_double * max(q, 1))(*[p[0] for p in pairs])
+        pr = (ctypes.c_double * max(q, 1))(*[p[1] for p in pairs])
+        ps = (ctypes.c_char_p * max(q, 1))(*[p.encode() for p in paths])
+        n_out, n_groups = np.zeros(max(q, 1), np.uint64), np.zeros(max(q, 1), np.uint64)
+        rc = load_library().rk_classify_db_pairs_to_csv(
+            self._h, db._h, lr, pr, q, ps, n_out.ctypes.data_as(_u64p),
+            n_groups.ctypes.data_as(_u64p))
+        if rc == -2:
+            raise RkError(rc, "Could not open an output path of " + ", ".join(paths))
+        if rc != RK_OK:
+            raise RkError(rc, self.last_error())
+        return [(int(n_out[i]), int(n_groups[i])) for i in range(q)]
+
+    def egress_stats(self) -> dict:
+        """The last device CSV save on this context (rk_get_egress_stats)."""
+        s = EgressStats()
+        _check(load_library().rk_get_egress_stats(self._h, ctypes.byref(s)))
+        return {k: getattr(s, k) for k, _ in EgressStats._fields_}
 
     def ingress_stats(self) -> dict:
         """The last device CSV load on this context (rk_get_ingress_stats)."""

@@ -1170,6 +1170,8 @@ extern "C" void rk_destroy(rk_ctx *ctx) {
   rk::batch_destroy(ctx);
   if (ctx->ws) (void)hipFree(ctx->ws);
   if (ctx->io) (void)hipFree(ctx->io);
+  for (void *p : ctx->txt)
+    if (p) (void)hipFree(p);
   if (ctx->ws_wide) (void)hipFree(ctx->ws_wide);
   if (ctx->kt.units) (void)hipFree(ctx->kt.units);
   if (ctx->ws_nw) (void)hipFree(ctx->ws_nw);

@@ -22,7 +22,12 @@
 // cache: no parse at all), --device-parse (the CSV body is
 // parsed on the GPU, rk_db_load_csv_device, and every pair is classified from
 // the columns that stay resident there: no second upload; --timing then adds
-// the ingress legs; not with --soa, --batch or --gpus above 1).
+// the ingress legs; not with --soa, --batch or --gpus above 1), --device-save
+// (only with --device-parse: all nine columns stay resident, RK_DB_KEEP_ROWS,
+// and every pair's output is formatted on the GPU and written from its staging
+// slots, rk_classify_db_pairs_to_csv: the result arrays never reach the host;
+// an output path that cannot be opened falls back to represults-<k>.csv as the
+// saver thread does; --timing then adds the egress legs).
 //
 //   rk_repkiller --batch <list> <len_ratio> <pos_ratio>
 //
@@ -45,7 +50,7 @@
 static void print_help() {
   std::printf("Repkiller (MI355X) v0.9.b-compatible\n");
   std::printf("Usage: ./rk_repkiller [--device N] [--gpus P [--same-device] [--comm rccl|local]] "
-              "[--timing] [--save-soa cache.soa | --soa | --device-parse] <input_file_path> <output_file_path> "
+              "[--timing] [--save-soa cache.soa | --soa | --device-parse [--device-save]] <input_file_path> <output_file_path> "
               "<length_ratio> <position_ratio> [<length_ratio> <position_ratio>]...\n");
   std::printf("       ./rk_repkiller [--device N] --batch <list of input<TAB>output lines> "
               "<length_ratio> <position_ratio>\n");
@@ -219,6 +224,7 @@ static int run_batch(const char *list_path, double lr, double pr, int device) {
 int main(int argc, char **argv) {
   int device = 0, gpus = 1;
   bool timing = false, same_device = false, soa_in = false, device_parse = false;
+  bool device_save = false;
   const char *comm_kind = nullptr, *save_soa = nullptr, *batch_list = nullptr;
   std::vector<const char *> pos;
   for (int i = 1; i < argc; ++i) {
@@ -229,6 +235,7 @@ int main(int argc, char **argv) {
     else if (!std::strcmp(argv[i], "--timing")) timing = true;
     else if (!std::strcmp(argv[i], "--soa")) soa_in = true;
     else if (!std::strcmp(argv[i], "--device-parse")) device_parse = true;
+    else if (!std::strcmp(argv[i], "--device-save")) device_save = true;
     else if (!std::strcmp(argv[i], "--save-soa") && i + 1 < argc) save_soa = argv[++i];
     else if (!std::strcmp(argv[i], "--batch") && i + 1 < argc) batch_list = argv[++i];
     else pos.push_back(argv[i]);
@@ -241,6 +248,11 @@ int main(int argc, char **argv) {
   }
   if (device_parse && (soa_in || batch_list || gpus != 1)) {
     std::fprintf(stderr, "--device-parse does not combine with --soa, --batch or --gpus.\n");
+    print_help();
+    return 1;
+  }
+  if (device_save && !device_parse) {
+    std::fprintf(stderr, "--device-save needs --device-parse.\n");
     print_help();
     return 1;
   }
@@ -299,7 +311,8 @@ int main(int argc, char **argv) {
       std::fprintf(stderr, "no usable gfx950 device %d (%d)\n", device, rc);
       return 1;
     }
-    rc = rk_db_load_csv_device(ctx, pos[0], RK_DB_KEEP_DEVICE, &db);
+    const uint32_t keep = device_save ? (uint32_t)RK_DB_KEEP_ROWS : (uint32_t)RK_DB_KEEP_DEVICE;
+    rc = rk_db_load_csv_device(ctx, pos[0], keep, &db);
     if (rc && rc != RK_E_IO && rc != RK_E_COUNT)
       std::fprintf(stderr, "device parse: %s\n", rk_last_error(ctx));
     if (rc) rk_destroy(ctx);
@@ -340,6 +353,71 @@ int main(int argc, char **argv) {
       rk_db_free(db);
       return 1;
     }
+  }
+  if (device_save) {
+    // classification and egress in one call per run; the file left behind is the
+    // last pair's, as below
+    const size_t q = params.size();
+    std::vector<double> lrs(q), prs(q);
+    std::vector<const char *> paths(q, out_path.c_str());
+    for (size_t i = 0; i < q; ++i) lrs[i] = params[i].first, prs[i] = params[i].second;
+    const double a = now_s();
+    rc = rk_classify_db_pairs_to_csv(ctx, db, lrs.data(), prs.data(), (uint32_t)q, paths.data(),
+                                     nullptr, nullptr);
+    if (rc == RK_E_IO) {
+      // the saver thread's rule, pair by pair (SaverQueue.cpp:16-20)
+      size_t fallback_count = 0;
+      rc = RK_OK;
+      for (size_t i = 0; i < q && !rc; ++i) {
+        const char *one = out_path.c_str();
+        rc = rk_classify_db_pairs_to_csv(ctx, db, &lrs[i], &prs[i], 1, &one, nullptr, nullptr);
+        if (rc != RK_E_IO) continue;
+        const std::string alt = "represults-" + std::to_string(++fallback_count) + ".csv";
+        std::fprintf(stderr, "Couldn't access %s, saving into %s\n", out_path.c_str(),
+                     alt.c_str());
+        one = alt.c_str();
+        rc = rk_classify_db_pairs_to_csv(ctx, db, &lrs[i], &prs[i], 1, &one, nullptr, nullptr);
+      }
+    }
+    const double t_all = now_s() - a;
+    if (rc) {
+      std::fprintf(stderr, "classification or device save failed (%d): %s\n", rc,
+                   rk_last_error(ctx));
+      rk_destroy(ctx);
+      rk_db_free(db);
+      return 1;
+    }
+    rk_stats stt{};
+    rk_get_stats(ctx, &stt);
+    rk_ingress_stats ing{};
+    rk_get_ingress_stats(ctx, &ing);
+    rk_egress_stats eg{};
+    rk_get_egress_stats(ctx, &eg);
+    rk_destroy(ctx);
+    if (timing) {
+      std::fprintf(stderr,
+                   "{\"ingress\": {\"body_bytes\": %llu, \"lines\": %llu, \"accepted\": %llu, "
+                   "\"host_lines\": %llu, \"windows\": %u, \"h2d_ms\": %.3f, \"device_ms\": %.3f, "
+                   "\"host_fix_ms\": %.3f, \"d2h_ms\": %.3f, \"total_ms\": %.3f}}\n",
+                   (unsigned long long)ing.body_bytes, (unsigned long long)ing.lines,
+                   (unsigned long long)ing.accepted, (unsigned long long)ing.host_lines,
+                   ing.windows, ing.h2d_ms, ing.device_ms, ing.host_fix_ms, ing.d2h_ms,
+                   ing.total_ms);
+      std::fprintf(stderr,
+                   "{\"egress\": {\"rows\": %llu, \"bytes\": %llu, \"host_rows\": %llu, "
+                   "\"chunks\": %u, \"upload_ms\": %.3f, \"device_ms\": %.3f, "
+                   "\"host_fix_ms\": %.3f, \"d2h_write_ms\": %.3f, \"total_ms\": %.3f}}\n",
+                   (unsigned long long)eg.rows, (unsigned long long)eg.bytes,
+                   (unsigned long long)eg.host_rows, eg.chunks, eg.upload_ms, eg.device_ms,
+                   eg.host_fix_ms, eg.d2h_write_ms, eg.total_ms);
+      std::fprintf(stderr,
+                   "{\"frags\": %llu, \"pairs\": %zu, \"load_s\": %.6f, "
+                   "\"classify_save_s\": %.6f, \"device_ms\": %.3f, \"gpus\": %d}\n",
+                   (unsigned long long)soa.n, params.size(), t1 - t0, t_all, stt.device_ms, gpus);
+    }
+    rk_db_free(db);
+    std::printf("Repkiller finished with no errors\n");
+    return 0;
   }
   rk_saver *sq = nullptr;
   rk_saver_start(db, &sq);

@@ -37,10 +37,43 @@
 #include <new>
 
 #include "rk_csv_line.h"
+#include "rk_csv_scan.h"
 #include "rk_ctx.h"
 #include "rk_db.h"
 
+namespace rk {
+
+int dev_alloc(rk_ctx *ctx, void **p, size_t bytes, const char *what) {
+  const hipError_t e = hipMalloc(p, bytes ? bytes : 16);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    *p = nullptr;
+    ctx->err = std::string(what) + " hipMalloc(" + std::to_string(bytes) + "): " +
+               hipGetErrorString(e);
+    return e == hipErrorOutOfMemory ? RK_E_NOMEM : RK_E_HIP;
+  }
+  return RK_OK;
+}
+
+// one of the context's grow-only buffers, at least `need` bytes
+int grow(rk_ctx *ctx, void **buf, size_t *cap, size_t need, const char *what) {
+  if (need <= *cap) return RK_OK;
+  if (*buf) (void)hipFree(*buf);
+  *buf = nullptr;
+  *cap = 0;
+  const int rc = dev_alloc(ctx, buf, need, what);
+  if (rc) return rc;
+  *cap = need;
+  return RK_OK;
+}
+
+}  // namespace rk
+
 namespace {
+
+using rk::dev_alloc;
+using rk::block_excl_scan;
+using rk::grow;
 
 // bytes of one line-index block: 128 lanes x 16 B.  Half of RK_CSV_MAX_LINE, so
 // a line the device parses can span three tiles.
@@ -79,24 +112,6 @@ __device__ inline uint32_t nl_mask(const char *buf, uint64_t off, uint64_t W) {
   return m;
 }
 
-// exclusive scan of v over the block's N threads; *total = the block's sum
-template <uint32_t N>
-__device__ inline uint32_t block_excl_scan(uint32_t v, uint32_t *lds, uint32_t *total) {
-  const uint32_t t = threadIdx.x;
-  lds[t] = v;
-  __syncthreads();
-  for (uint32_t d = 1; d < N; d <<= 1) {
-    const uint32_t a = t >= d ? lds[t - d] : 0u;
-    __syncthreads();
-    lds[t] += a;
-    __syncthreads();
-  }
-  const uint32_t incl = lds[t];
-  *total = lds[N - 1];
-  __syncthreads();
-  return incl - v;
-}
-
 __global__ __launch_bounds__(TI) void k_csv_nl_count(const char *buf, uint64_t W,
                                                     uint32_t *tile_cnt) {
   const uint64_t off = (uint64_t)blockIdx.x * TILE + threadIdx.x * 16u;
@@ -105,30 +120,6 @@ __global__ __launch_bounds__(TI) void k_csv_nl_count(const char *buf, uint64_t W
   uint32_t sum;
   (void)block_excl_scan<TI>((uint32_t)__popc(nl_mask(buf, off, W)), lds, &sum);
   if (threadIdx.x == 0) tile_cnt[blockIdx.x] = sum;
-}
-
-// out[i] = in[0] + ... + in[i-1] for i in [0, n]; one block
-__global__ __launch_bounds__(1024) void k_csv_scan(const uint32_t *in, uint64_t n, uint64_t *out) {
-  __shared__ uint64_t s[1024];
-  const uint32_t t = threadIdx.x;
-  const uint64_t chunk = (n + 1023) / 1024;
-  const uint64_t lo = min(n, (uint64_t)t * chunk), hi = min(n, lo + chunk);
-  uint64_t sum = 0;
-  for (uint64_t i = lo; i < hi; ++i) sum += in[i];
-  s[t] = sum;
-  __syncthreads();
-  for (uint32_t d = 1; d < 1024; d <<= 1) {
-    const uint64_t a = t >= d ? s[t - d] : 0ull;
-    __syncthreads();
-    s[t] += a;
-    __syncthreads();
-  }
-  uint64_t run = s[t] - sum;
-  for (uint64_t i = lo; i < hi; ++i) {
-    out[i] = run;
-    run += in[i];
-  }
-  if (t == 1023) out[n] = s[1023];
 }
 
 // start[k] = body offset of line k; the '\n' that ends line k writes
@@ -269,30 +260,6 @@ void free_dev_block(void *block, int device) {
   (void)hipFree(block);
 }
 
-int dev_alloc(rk_ctx *ctx, void **p, size_t bytes, const char *what) {
-  const hipError_t e = hipMalloc(p, bytes ? bytes : 16);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    *p = nullptr;
-    ctx->err = std::string(what) + " hipMalloc(" + std::to_string(bytes) + "): " +
-               hipGetErrorString(e);
-    return e == hipErrorOutOfMemory ? RK_E_NOMEM : RK_E_HIP;
-  }
-  return RK_OK;
-}
-
-// one of the context's grow-only buffers, at least `need` bytes
-int grow(rk_ctx *ctx, void **buf, size_t *cap, size_t need, const char *what) {
-  if (need <= *cap) return RK_OK;
-  if (*buf) (void)hipFree(*buf);
-  *buf = nullptr;
-  *cap = 0;
-  const int rc = dev_alloc(ctx, buf, need, what);
-  if (rc) return rc;
-  *cap = need;
-  return RK_OK;
-}
-
 Cols carve_cols(rk::Carve &c, uint64_t n) {
   Cols k;
   k.xs = c.take<uint64_t>(n), k.ys = c.take<uint64_t>(n), k.xe = c.take<uint64_t>(n);
@@ -430,7 +397,7 @@ struct Load {
     if ((rc = timed_begin())) return rc;
     HIPCHK(ctx, hipMemsetAsync(cnt, 0, 8 * sizeof(unsigned long long), s));
     k_csv_nl_count<<<(uint32_t)ntiles, TI, 0, s>>>(raw, W, tile_cnt);
-    k_csv_scan<<<1, 1024, 0, s>>>(tile_cnt, ntiles, tile_pre);
+    rk::k_csv_scan<uint64_t><<<1, 1024, 0, s>>>(tile_cnt, ntiles, tile_pre);
     uint64_t newlines = 0;
     HIPCHK(ctx, hipMemcpyAsync(ctx->host, tile_pre + ntiles, 8, hipMemcpyDeviceToHost, s));
     if ((rc = timed_end())) return rc;
@@ -554,7 +521,7 @@ struct Load {
     if (lines) {
       if ((rc = timed_begin())) return rc;
       k_csv_flagcount<<<(uint32_t)nblk, TB, 0, s>>>(status, lines, blk_cnt);
-      k_csv_scan<<<1, 1024, 0, s>>>(blk_cnt, nblk, blk_pre);
+      rk::k_csv_scan<uint64_t><<<1, 1024, 0, s>>>(blk_cnt, nblk, blk_pre);
       k_csv_scatter<<<(uint32_t)nblk, TB, 0, s>>>(status, lines, blk_pre, out_n, out_cap, stg,
                                                   fin);
       if ((rc = timed_end())) return rc;
@@ -590,9 +557,11 @@ int load_device(rk_ctx *ctx, const char *path, uint32_t flags, rk_db **out) {
 
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const bool keep = flags & RK_DB_KEEP_DEVICE;
+  const bool keep_rows = flags == RK_DB_KEEP_ROWS;
   if (keep) {
     db->dev_free = free_dev_block;
     db->dev_device = ctx->device;
+    db->dev_rows = keep_rows;
   }
   uint64_t n = 0;
   if (body_bytes) {
@@ -600,15 +569,17 @@ int load_device(rk_ctx *ctx, const char *path, uint32_t flags, rk_db **out) {
     const uint64_t cap = std::min<uint64_t>(db->total_hdr, body_bytes / 7 + 1);
     // the database's own columns: x_start, y_start, length, strand (kept with
     // RK_DB_KEEP_DEVICE) and the five others
+    // (with RK_DB_KEEP_ROWS one allocation holds both blocks, the five others
+    // behind the four: the database's one dev_free hook releases all nine)
     DevBuf kept, rest;
     rk::Carve pk{nullptr}, pr{nullptr};
     pk.take<uint64_t>(cap), pk.take<uint64_t>(cap), pk.take<uint64_t>(cap), pk.take<uint8_t>(cap);
     pr.take<uint64_t>(cap), pr.take<uint64_t>(cap), pr.take<uint64_t>(cap), pr.take<uint64_t>(cap);
     pr.take<float>(cap);
     int rc;
-    if ((rc = dev_alloc(ctx, &kept.p, pk.off, "csv columns"))) return rc;
-    if ((rc = dev_alloc(ctx, &rest.p, pr.off, "csv columns"))) return rc;
-    rk::Carve ck{(char *)kept.p}, cr{(char *)rest.p};
+    if ((rc = dev_alloc(ctx, &kept.p, pk.off + (keep_rows ? pr.off : 0), "csv columns"))) return rc;
+    if (!keep_rows && (rc = dev_alloc(ctx, &rest.p, pr.off, "csv columns"))) return rc;
+    rk::Carve ck{(char *)kept.p}, cr{keep_rows ? (char *)kept.p + pk.off : (char *)rest.p};
     Load L{ctx, p};
     L.fin.xs = ck.take<uint64_t>(cap), L.fin.ys = ck.take<uint64_t>(cap);
     L.fin.len = ck.take<uint64_t>(cap), L.fin.strand = ck.take<uint8_t>(cap);
@@ -671,6 +642,10 @@ int load_device(rk_ctx *ctx, const char *path, uint32_t flags, rk_db **out) {
       kept.p = nullptr;
       db->dev_x = L.fin.xs, db->dev_y = L.fin.ys, db->dev_len = L.fin.len;
       db->dev_strand = L.fin.strand;
+      if (keep_rows) {
+        db->dev_xe = L.fin.xe, db->dev_ye = L.fin.ye, db->dev_score = L.fin.score;
+        db->dev_ident = L.fin.ident, db->dev_sim = L.fin.sim;
+      }
     }
   }
   st.accepted = n;
@@ -682,7 +657,8 @@ int load_device(rk_ctx *ctx, const char *path, uint32_t flags, rk_db **out) {
 }  // namespace
 
 extern "C" int rk_db_load_csv_device(rk_ctx *ctx, const char *path, uint32_t flags, rk_db **out) {
-  if (!ctx || !path || !out || (flags & ~(uint32_t)RK_DB_KEEP_DEVICE)) return RK_E_ARG;
+  // flags: 0, RK_DB_KEEP_DEVICE or RK_DB_KEEP_ROWS (bit 1 alone keeps nothing to classify)
+  if (!ctx || !path || !out || (flags & ~(uint32_t)RK_DB_KEEP_ROWS) || flags == 2) return RK_E_ARG;
   *out = nullptr;
   ctx->err.clear();
   try {
@@ -705,6 +681,35 @@ extern "C" int rk_get_ingress_stats(const rk_ctx *ctx, rk_ingress_stats *st) {
 extern "C" uint32_t rk_csv_max_line(void) { return RK_CSV_MAX_LINE; }
 extern "C" uint32_t rk_csv_tile(void) { return TILE; }
 
+// Classify `db` from its resident columns; dres[q] are DEVICE arrays carved
+// from ctx->io (valid until the context's next call that stages through it).
+// Returns with the stream idle.
+int rk::db_classify_resident(rk_ctx *ctx, const rk_db *db, const double *len_ratio,
+                             const double *pos_ratio, uint32_t npairs,
+                             std::vector<rk_result> &dres) {
+  rk_frags_soa dv;
+  if (rk_db_device_view(db, &dv)) return RK_E_ARG;
+  const size_t n = dv.n;
+  if (n >= 0xFFFFFFFFull) return RK_E_TOO_MANY;
+  // per pair gid, order (u32), rep (u8) out, as rk_classify_pairs stages them
+  const size_t need = (size_t)npairs * (rk::align_up(n + 16) + rk::align_up(n * 4 + 16) * 2);
+  int rc = grow(ctx, &ctx->io, &ctx->io_cap, need, "result staging");
+  if (rc) return rc;
+  rk::Carve c{(char *)ctx->io};
+  dres.assign(npairs, rk_result{});
+  std::vector<rk_params> ps(npairs);
+  for (uint32_t q = 0; q < npairs; ++q) {
+    uint8_t *drep = c.take<uint8_t>(n);
+    uint32_t *dgid = c.take<uint32_t>(n), *dord = c.take<uint32_t>(n);
+    dres[q] = rk_result{dord, dgid, drep, 0, 0};
+    ps[q] = rk_params{db->len_x_hdr, db->len_y_hdr, len_ratio[q], pos_ratio[q]};
+  }
+  rc = rk_classify_device_pairs(ctx, &dv, ps.data(), npairs, dres.data());
+  if (rc) return rc;
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  return RK_OK;
+}
+
 extern "C" int rk_classify_db_pairs(rk_ctx *ctx, const rk_db *db, const double *len_ratio,
                                     const double *pos_ratio, uint32_t npairs, rk_result *out) {
   if (!ctx || !db || !len_ratio || !pos_ratio || !out || npairs == 0) return RK_E_ARG;
@@ -721,23 +726,9 @@ extern "C" int rk_classify_db_pairs(rk_ctx *ctx, const rk_db *db, const double *
   }
   HIPCHK(ctx, hipSetDevice(ctx->device));
   try {
-    // per pair gid, order (u32), rep (u8) out, as rk_classify_pairs stages them
-    const size_t need =
-        (size_t)npairs * (rk::align_up(n + 16) + rk::align_up(n * 4 + 16) * 2);
-    int rc = grow(ctx, &ctx->io, &ctx->io_cap, need, "result staging");
+    std::vector<rk_result> dres;
+    int rc = rk::db_classify_resident(ctx, db, len_ratio, pos_ratio, npairs, dres);
     if (rc) return rc;
-    rk::Carve c{(char *)ctx->io};
-    std::vector<rk_result> dres(npairs);
-    std::vector<rk_params> ps(npairs);
-    for (uint32_t q = 0; q < npairs; ++q) {
-      uint8_t *drep = c.take<uint8_t>(n);
-      uint32_t *dgid = c.take<uint32_t>(n), *dord = c.take<uint32_t>(n);
-      dres[q] = rk_result{dord, dgid, drep, 0, 0};
-      ps[q] = rk_params{db->len_x_hdr, db->len_y_hdr, len_ratio[q], pos_ratio[q]};
-    }
-    rc = rk_classify_device_pairs(ctx, &dv, ps.data(), npairs, dres.data());
-    if (rc) return rc;
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     const double t2 = rk::wall_ms();
     std::vector<rk::IoPiece> down;
     for (uint32_t q = 0; q < npairs; ++q) {

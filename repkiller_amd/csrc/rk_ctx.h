@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstring>
+#include <functional>
 #include <string>
 #include <thread>
 #include <vector>
@@ -60,6 +61,9 @@ struct rk_ctx {
   const rk::BatchTables *batch_tables = nullptr;
   rk_batch_stats batch_stats{};
   rk_ingress_stats ingress{};  // the last rk_db_load_csv_device (rk_csv.hip)
+  rk_egress_stats egress{};    // the last rk_db_write_csv_device (rk_csv_out.hip)
+  void *txt[2] = {};           // its two chunk text buffers, grow-only
+  size_t txt_cap[2] = {};
   // the sharded driver's fast path (rk_shard_fast.h): its all-gather messages
   // (pinned, every rank's), the stage fingerprints of the last call that
   // completed on it (a stage whose gathered counts match needs no agreement
@@ -84,7 +88,13 @@ struct rk_ctx {
   uint64_t kt_launches[rk::KID_COUNT] = {};
 };
 
+struct rk_db;
+
 namespace rk {
+
+// rk_csv.hip: the body of rk_classify_db_pairs up to the download
+int db_classify_resident(rk_ctx *ctx, const rk_db *db, const double *len_ratio,
+                         const double *pos_ratio, uint32_t npairs, std::vector<rk_result> &dres);
 
 #define HIPCHK(ctx, call)                                                          \
   do {                                                                             \
@@ -120,6 +130,14 @@ struct IoPiece {
 };
 int io_h2d(rk_ctx *ctx, const std::vector<IoPiece> &pieces);
 int io_d2h(rk_ctx *ctx, const std::vector<IoPiece> &pieces);
+// device -> consumer: `bytes` bytes at dev come down through the pinned slots
+// and each filled slot goes to sink(data, len, off) (off: the slot's offset in
+// the piece) on a writer pool of at most 4 threads; a slot is issued again only
+// after its sink call has returned.  Before the first copy the copy stream
+// waits for `ready` (null: nothing to wait for).  Returns when every sink call
+// has; 1 when a sink call returned false (the rest are then skipped).
+int io_d2h_sink(rk_ctx *ctx, const void *dev, size_t bytes, hipEvent_t ready,
+                const std::function<bool(const char *, size_t, size_t)> &sink);
 // the rows of a host SoA as 12-B wire records {xStart lo, yStart lo, length
 // (24) | reverse (1) | yStart >> 32 (3) | xStart >> 32 (4)} at `dev`, packed by
 // the host threads into the staging ring; 1 when some row does not fit
@@ -146,6 +164,10 @@ inline void stats_numa_unknown(rk_stats *st) {
   st->numa_input = st->numa_threads = st->numa_staging = st->numa_gpu = -1;
 }
 bool host_pinned(const void *p);
+// rk_csv.hip: hipMalloc with the failure put in ctx->err (RK_E_NOMEM / RK_E_HIP),
+// and one of the context's grow-only buffers brought to at least `need` bytes
+int dev_alloc(rk_ctx *ctx, void **p, size_t bytes, const char *what);
+int grow(rk_ctx *ctx, void **buf, size_t *cap, size_t need, const char *what);
 double wall_ms();
 
 // copy `count` device words into ctx->host and wait

@@ -18,6 +18,11 @@ struct rk_db {
   void *dev_block = nullptr;
   const uint64_t *dev_x = nullptr, *dev_y = nullptr, *dev_len = nullptr;
   const uint8_t *dev_strand = nullptr;
+  // with RK_DB_KEEP_ROWS the other five columns stay too (a second carve of the
+  // same allocation, so the one dev_free hook releases all nine); null otherwise
+  const uint64_t *dev_xe = nullptr, *dev_ye = nullptr, *dev_score = nullptr, *dev_ident = nullptr;
+  const float *dev_sim = nullptr;
+  bool dev_rows = false;  // loaded with RK_DB_KEEP_ROWS (also when it has no rows)
   int dev_device = -1;
   void (*dev_free)(void *block, int device) = nullptr;
 };
@@ -36,5 +41,9 @@ bool db_parse_line(const char *b, const char *e, DbRow *r);
 // three header numbers (std::getline semantics); returns where the body starts,
 // *eof set when the file ended inside the header
 const char *db_read_header(rk_db *db, const char *p, const char *end, bool *eof);
+// rk_host.cpp: output row of input row i (store_frag, commonFunctions.cpp:101-104)
+// at o, at most 255 bytes; returns the end.  The device egress (rk_csv_out.hip)
+// formats with it the rows its own row function refuses.
+char *db_format_row(const rk_db *db, uint32_t i, uint64_t gid, unsigned rep, char *o);
 
 }  // namespace rk

@@ -612,6 +612,10 @@ int write_csv(const rk_db *db, const char *path, const uint32_t *gid, const uint
 
 }  // namespace
 
+char *rk::db_format_row(const rk_db *db, uint32_t i, uint64_t gid, unsigned rep, char *o) {
+  return format_row(o, db, i, gid, rep);
+}
+
 extern "C" int rk_db_write_csv(const rk_db *db, const char *path, const rk_result *res) {
   if (!db || !path || !res || (res->n_out && (!res->gid || !res->repval || !res->out_order)))
     return RK_E_ARG;

@@ -363,6 +363,53 @@ int io_d2h(rk_ctx *ctx, const std::vector<IoPiece> &pieces) {
   return RK_OK;
 }
 
+// Device -> consumer.  Writer w of at most NSLOT (4) owns slot w and takes the
+// SLOT-sized pieces w, w + NSLOT, ...: copy into the slot, wait for it, hand it
+// to the sink.  A slot is therefore issued again only after its sink call has
+// returned, and while one writer sits in its sink (a pwrite) the others' copies
+// and sinks go on: the bytes go device -> pinned slot -> consumer with no host
+// copy in between.
+int io_d2h_sink(rk_ctx *ctx, const void *dev, size_t bytes, hipEvent_t ready,
+                const std::function<bool(const char *, size_t, size_t)> &sink) {
+  int rc = io_ready(ctx);
+  if (rc) return rc;
+  IoEngine &e = *ctx->ioe;
+  if (ready) HIPCHK(ctx, hipStreamWaitEvent(e.io, ready, 0));
+  const size_t nc = (bytes + SLOT - 1) / SLOT;
+  const int nw = (int)std::min<size_t>(nc, (size_t)NSLOT);
+  std::atomic<bool> sink_bad{false};
+  hipError_t herr[NSLOT] = {};
+  bool unstarted[NSLOT] = {};
+  auto writer = [&](int w) {
+    hipError_t h = hipSetDevice(ctx->device);
+    for (size_t i = (size_t)w; i < nc && h == hipSuccess && !sink_bad; i += NSLOT) {
+      const size_t off = i * SLOT, len = std::min(SLOT, bytes - off);
+      h = hipMemcpyAsync(e.slot[w], (const char *)dev + off, len, hipMemcpyDeviceToHost, e.io);
+      if (h == hipSuccess) h = hipEventRecord(e.ev[w], e.io);
+      if (h == hipSuccess) h = hipEventSynchronize(e.ev[w]);
+      if (h == hipSuccess && !sink(e.slot[w], len, off)) sink_bad = true;
+    }
+    herr[w] = h;
+  };
+  {
+    std::vector<std::thread> th;
+    for (int w = 1; w < nw; ++w) {
+      try {
+        th.emplace_back(writer, w);
+      } catch (...) {  // no thread to be had: this one takes the slot's pieces below
+        unstarted[w] = true;
+      }
+    }
+    if (nw) writer(0);
+    for (auto &t : th) t.join();
+    for (int w = 1; w < nw; ++w)
+      if (unstarted[w]) writer(w);
+  }
+  HIPCHK(ctx, hipStreamSynchronize(e.io));
+  for (int w = 0; w < nw; ++w) HIPCHK(ctx, herr[w]);
+  return sink_bad ? 1 : RK_OK;
+}
+
 int io_h2d_rows(rk_ctx *ctx, const rk_frags_soa &in, void *dev) {
   int rc = io_ready(ctx);
   if (rc) return rc;

@@ -10,6 +10,12 @@ one synthetic file, next to the reference itself (oracle/_ref/ref_driver,
 1 core) on the same file, and checks that both outputs are byte-identical.
 
   python tools/io_bench.py [--n 50000000] [--genome 3000000000] [--tmp DIR]
+                           [--device-parse-reps K [--egress-rows R1,R2,...]]
+
+--device-parse-reps K alternates three routes K times each on the same file:
+host (parse, classify, format on the host side of PCIe), device (parsed on the
+GPU, formatted by the host) and device_save (parsed, classified and formatted
+on the GPU); every output's SHA-256 is compared with the host route's.
 
 (default: cfg3, the headline config: 50M fragments over 3 Gbp)
 
@@ -50,23 +56,60 @@ def sha256_file(path):
     return h.hexdigest()
 
 
-def device_parse_leg(ctx, inp, d, host_csv, reps):
-    """The host route (rk_db_load_csv -> rk_classify -> rk_db_write_csv) and the
+def rounded(st):
+    return {k: (round(v, 3) if isinstance(v, float) else v) for k, v in st.items()}
+
+
+def device_parse_leg(ctx, inp, d, host_csv, reps, egress_rows=()):
+    """The host route (rk_db_load_csv -> rk_classify -> rk_db_write_csv), the
     device-parse route (rk_db_load_csv_device with the columns kept resident ->
-    rk_classify_db_pairs -> rk_db_write_csv) on the same file, alternating,
-    page cache warm for both.  The host route is the yardstick: it is timed
-    here, in the same job on the same box."""
+    rk_classify_db_pairs -> rk_db_write_csv) and the device-save route (all nine
+    columns resident -> rk_classify_db_pairs_to_csv: classified and formatted on
+    the device, no separate save) on the same file, alternating, page cache
+    warm for all.  The host route is the yardstick of the parse, the device
+    route of the save: both are timed here, in the same job on the same box.
+    egress_rows: RK_CSV_OUT_ROWS candidates, each timed once more per rep on the
+    device-save route's database (the environment is restored afterwards)."""
     want = sha256_file(host_csv)
-    legs = {"host": [], "device": []}
+    legs = {"host": [], "device": [], "device_save": []}
+    sweep = {str(r): [] for r in egress_rows}
     for _ in range(reps):
-        for route in ("host", "device"):
+        for route in ("host", "device", "device_save"):
             out_csv = os.path.join(d, f"leg_{route}.csv")
             t0 = time.perf_counter()
             if route == "host":
                 db = rk.FragmentsDatabase(inp)
             else:
-                db = rk.FragmentsDatabase(inp, ctx=ctx, keep_device=True)
+                db = rk.FragmentsDatabase(inp, ctx=ctx, keep_device=True,
+                                          keep_rows=route == "device_save")
             t1 = time.perf_counter()
+            if route == "device_save":
+                ctx.classify_db_to_csv(db, [(0.3, 0.3)], [out_csv])
+                t3 = time.perf_counter()
+                leg = {"load_s": round(t1 - t0, 3), "classify_save_s": round(t3 - t1, 3),
+                       "total_s": round(t3 - t0, 3), "egress": rounded(ctx.egress_stats()),
+                       "classify_device_ms": round(ctx.stats()["device_ms"], 3)}
+                leg["ingress"] = rounded(ctx.ingress_stats())
+                leg["same_csv_as_host_route"] = sha256_file(out_csv) == want
+                os.remove(out_csv)
+                saved = os.environ.get("RK_CSV_OUT_ROWS")
+                for r in egress_rows:
+                    os.environ["RK_CSV_OUT_ROWS"] = str(r)
+                    t4 = time.perf_counter()
+                    ctx.classify_db_to_csv(db, [(0.3, 0.3)], [out_csv])
+                    t5 = time.perf_counter()
+                    sweep[str(r)].append({"classify_save_s": round(t5 - t4, 3),
+                                          "egress": rounded(ctx.egress_stats()),
+                                          "same_csv_as_host_route": sha256_file(out_csv) == want})
+                    os.remove(out_csv)
+                if saved is None:
+                    os.environ.pop("RK_CSV_OUT_ROWS", None)
+                else:
+                    os.environ["RK_CSV_OUT_ROWS"] = saved
+                db.close()
+                del db
+                legs[route].append(leg)
+                continue
             if route == "host":
                 res = ctx.classify(db.frags, db.len_x_hdr, db.len_y_hdr, 0.3, 0.3)
             else:
@@ -95,7 +138,19 @@ def device_parse_leg(ctx, inp, d, host_csv, reps):
         summary[route] = {"total_s_median": tot[len(tot) // 2], "total_s_min": tot[0],
                           "total_s_max": tot[-1],
                           "load_s_median": sorted(r["load_s"] for r in runs)[len(runs) // 2]}
-    return {"reps": reps, "legs": legs, "summary": summary, "host_csv_sha256": want}
+    # the device-save route counts as faster than the device route only when its
+    # median total is below that route's median by more than that route's spread
+    dv, ds = summary["device"], summary["device_save"]
+    summary["device_save_faster_than_device"] = bool(
+        dv["total_s_median"] - ds["total_s_median"] > dv["total_s_max"] - dv["total_s_min"])
+    cs = sorted(r["classify_s"] + r["save_s"] for r in legs["device"])
+    dv["classify_plus_save_s_median"] = round(cs[len(cs) // 2], 3)
+    cs = sorted(r["classify_save_s"] for r in legs["device_save"])
+    ds["classify_save_s_median"] = cs[len(cs) // 2]
+    out = {"reps": reps, "legs": legs, "summary": summary, "host_csv_sha256": want}
+    if sweep:
+        out["egress_rows_sweep"] = sweep
+    return out
 
 
 def main():
@@ -109,6 +164,12 @@ def main():
     ap.add_argument("--device-parse-reps", type=int, default=0,
                     help="alternate the host route and the device-parse route this many times "
                          "each on the same file (warm page cache) and record both")
+    ap.add_argument("--egress-rows", default="",
+                    help="comma-separated RK_CSV_OUT_ROWS candidates, each timed on the "
+                         "device-save route in every rep")
+    ap.add_argument("--device-save-only", type=int, default=0,
+                    help="load once with every column resident, classify and save on the "
+                         "device this many times, and stop (a run for a kernel trace)")
     ap.add_argument("--tmp", default=os.environ.get("TMPDIR", "/tmp"))
     args = ap.parse_args()
     n, L = args.n, args.genome
@@ -134,6 +195,16 @@ def main():
         del f
         out["csv_bytes"] = os.path.getsize(inp)
         ctx = rk.Context(0)
+        if args.device_save_only > 0:
+            db = rk.FragmentsDatabase(inp, ctx=ctx, keep_rows=True)
+            runs = []
+            for _ in range(args.device_save_only):
+                ctx.classify_db_to_csv(db, [(0.3, 0.3)], [os.path.join(d, "save.csv")])
+                runs.append(rounded(ctx.egress_stats()))
+            db.close()
+            stop.set()
+            print(json.dumps({"fragments": n, "device_save_only": runs}), flush=True)
+            return
         t0 = time.perf_counter()
         db = rk.FragmentsDatabase(inp)
         t1 = time.perf_counter()
@@ -167,7 +238,8 @@ def main():
         del db2, res2
         if args.device_parse_reps > 0:
             del db, res
-            out["device_parse"] = device_parse_leg(ctx, inp, d, ours, args.device_parse_reps)
+            rows = [int(r) for r in args.egress_rows.split(",") if r]
+            out["device_parse"] = device_parse_leg(ctx, inp, d, ours, args.device_parse_reps, rows)
         ref = os.path.join(ROOT, "oracle", "_ref", "ref_driver")
         if not args.no_ref and os.path.exists(ref):
             theirs = os.path.join(d, "ref.csv")
