@@ -117,7 +117,7 @@ int resolve_axis(rk_ctx *ctx, const Axis &ax, SweepScratch sc, bool fast32, uint
   uint32_t *counters = sc.counters;
   uint8_t *rpend = sc.rpend;
   RunList rl{sc.runs, sc.wpend, 0, 0, fast32};
-  build_runs(ax, rl, sc.dev_count, ctx->host + 128, ctx->stream);
+  build_runs(ax, rl, sc.dev_count, ctx->host + HOST_SCRATCH, ctx->stream);
   HIPCHK(ctx, hipGetLastError());
   // the 32-bit path's first sweep sets the open flag of every long run itself
   if (!fast32) HIPCHK(ctx, hipMemsetAsync(rpend, 1, ax.m, ctx->stream));
@@ -165,7 +165,8 @@ int resolve_axis_queued(rk_ctx *ctx, const Axis &ax, SweepScratch sc, uint32_t s
                         uint32_t *pend, uint32_t *junk) {
   if (!ax.m) return RK_OK;
   RunList rl{sc.runs, sc.wpend, 0, 0, true};
-  build_runs(ax, rl, sc.dev_count, ctx->host + 128, ctx->stream);  // (32-bit: no readback)
+  // (32-bit: no readback)
+  build_runs(ax, rl, sc.dev_count, ctx->host + HOST_SCRATCH, ctx->stream);
   // junk: the sweeps before the last count into words nobody reads, and the
   // last one into sc.counters, already zero (no clear launched per sweep)
   for (uint32_t s = 0; s < sweeps; ++s)
@@ -196,7 +197,7 @@ struct Plan {
 };
 
 struct Work {
-  uint32_t *ctrl;  // [0] err bits, [1] kept rows, [2..7] counters
+  uint32_t *ctrl;  // CW_GENERIC_WORDS control words (CW_*, rk_ctrl.h)
   uint32_t *pkey_in, *tk, *tv, *tk2, *tv2;
   uint32_t *radix, *radix2;
   size_t radix_words;
@@ -213,7 +214,7 @@ struct Work {
 
 size_t carve(Carve &c, const Plan &pl, Work &w) {
   const size_t n = pl.n + 1;
-  w.ctrl = c.take<uint32_t>(64 + rk::PEND_WORDS);
+  w.ctrl = c.take<uint32_t>(rk::CW_GENERIC_WORDS);
   w.pkey_in = c.take<uint32_t>(n);
   w.tk = c.take<uint32_t>(n);
   w.tv = c.take<uint32_t>(n);
@@ -290,8 +291,8 @@ int ensure_ws(rk_ctx *ctx, const Plan &pl, Work &w) {
 }
 
 rk::SweepScratch sweep_scratch(const Work &w) {
-  return rk::SweepScratch{w.runs, w.wpend, reinterpret_cast<uint8_t *>(w.rpend), w.ctrl + 64,
-                          w.ctrl + 2};
+  return rk::SweepScratch{w.runs, w.wpend, reinterpret_cast<uint8_t *>(w.rpend),
+                          w.ctrl + rk::CW_PEND_X, w.ctrl + rk::CW_SWEEP_COUNT};
 }
 
 // The 64-bit centre/length copies of both axes and the Y lengths' high words,
@@ -423,10 +424,8 @@ size_t carve_nw(Carve &c, uint64_t n1, uint32_t nbx, NWork &w) {
 // control words and digit histograms (ctrl, ahist / yhist / ehist), size
 // independent of n: the upfront pass that decides whether every row packs
 // writes only these, so an input that falls back never sizes the workspace
-// ctrl: 64 words, the X and the Y axis' pending counters (zeroed with the
-// words), a third counter block the earlier queued sweeps count into (never
-// read), then the order / Y / member histograms
-constexpr size_t NW_CTRL_WORDS = 64 + 3 * rk::PEND_WORDS;
+// ctrl: the record block (rk_ctrl.h), then the order / Y / member histograms
+constexpr size_t NW_CTRL_WORDS = rk::CW_RECORD_WORDS;
 constexpr size_t NW_SMALL_WORDS = NW_CTRL_WORDS + 3 * 4096;
 
 int ensure_nw_small(rk_ctx *ctx, NWork &w) {
@@ -561,26 +560,26 @@ int classify_narrow(rk_ctx *ctx, const rk_frags_soa *in, const rk_params *prms, 
   HIPCHK(ctx, hipEventRecord(ctx->ev0, st));
   // the control words and the order / Y / member digit histograms (ehist stays
   // zero until the first pair's k_nw_assign), one launch
-  rk::zero_regions(st, {{w.ctrl, (64 + 2 * rk::PEND_WORDS) * sizeof(uint32_t)},
+  rk::zero_regions(st, {{w.ctrl, rk::CW_CLEARED_WORDS * sizeof(uint32_t)},
                         {w.ahist, 3 * 4096 * sizeof(uint32_t)}, cr[0], cr[1], cr[2], cr[3]});
   mark(ctx, RK_PH_PREP);
   rk::nw_order_hist(*in, pl.vsize, pl.max_x, pl.max_y, pl.nby, split ? op.coarse : ad,
                     ysplit ? yp.coarse : yd, w.ahist, w.yhist, w.ctrl, st, wire);
   HIPCHK(ctx, hipGetLastError());
   if (early) {
-    HIPCHK(ctx, hipMemcpyAsync(ctx->host, w.ctrl, 9 * sizeof(uint32_t), hipMemcpyDeviceToHost,
-                               st));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->host, w.ctrl + rk::RB_ORDER, rk::RB_ORDER_N * sizeof(uint32_t),
+                               hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipEventRecord(ctx->aux, st));
     mark(ctx, RK_PH_ORDER);
     rk::nw_order_sort_split_coarse(*in, op, w.ahist, w.astatus, w.Ra, w.Rb, w.chist,
                                    rk::ZeroRegion{}, pl.vsize, st, wire, true);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipEventSynchronize(ctx->aux));
-  } else if ((rc = readback(ctx, w.ctrl, 9))) {
+  } else if ((rc = readback(ctx, w.ctrl + rk::RB_ORDER, rk::RB_ORDER_N))) {
     return rc;
   }
-  if ((rc = err_status(ctx, ctx->host[0]))) return rc;
-  if (ctx->host[3]) {  // some row does not pack into a record
+  if ((rc = err_status(ctx, ctx->host[rk::CW_ERR - rk::RB_ORDER]))) return rc;
+  if (ctx->host[rk::CW_NOPACK - rk::RB_ORDER]) {  // some row does not pack into a record
     *fallback = true;
     ctx->stats.record_fallback = 1;
     ctx->nw_fell_back = true;
@@ -590,7 +589,8 @@ int classify_narrow(rk_ctx *ctx, const rk_frags_soa *in, const rk_params *prms, 
   // every row packs: now the workspace (~190 B per row)
   if (!early && (rc = ensure_nw(ctx, pl.n, pl.nbx, w))) return rc;
   rk::ScanScratch ss{w.scan, w.scan_cap};
-  const uint32_t m = ctx->host[1], maxlen = ctx->host[4];
+  const uint32_t m = ctx->host[rk::CW_KEPT - rk::RB_ORDER],
+                 maxlen = ctx->host[rk::CW_MAXLEN - rk::RB_ORDER];
   ctx->stats.n_proc = m;
   for (uint32_t q = 0; q < npairs; ++q) outs[q].n_out = m, outs[q].n_groups = 0;
   if (m == 0) {
@@ -641,18 +641,18 @@ int classify_narrow(rk_ctx *ctx, const rk_frags_soa *in, const rk_params *prms, 
   if (ctx->batch_tables) rk::batch_nbd(*ctx->batch_tables, false, w.cx, m, pl.nbx, st);
   HIPCHK(ctx, hipGetLastError());
   mark(ctx, RK_PH_OCC_CSR);
-  // pending counters: the X axis' at ctrl[64..), the Y axis' after them (both
-  // zero from the call's start), a third block for the queued sweeps before
-  // each axis' last (never read)
-  rk::SweepScratch sc{w.runs, w.wpend, reinterpret_cast<uint8_t *>(w.rpend), w.ctrl + 64,
-                      w.ctrl + 2};
+  // pending counters: the X axis', the Y axis' after them (both zero from the
+  // call's start), a third block for the queued sweeps before each axis' last
+  // (never read)
+  rk::SweepScratch sc{w.runs, w.wpend, reinterpret_cast<uint8_t *>(w.rpend),
+                      w.ctrl + rk::CW_PEND_X, w.ctrl + rk::CW_SWEEP_COUNT};
   rk::SweepScratch scy = sc;
-  scy.counters = w.ctrl + 64 + rk::PEND_WORDS;
-  uint32_t *const junk = w.ctrl + 64 + 2 * rk::PEND_WORDS;
+  scy.counters = w.ctrl + rk::CW_PEND_Y;
+  uint32_t *const junk = w.ctrl + rk::CW_PEND_JUNK;
   // Both axes' sweeps are queued without a host round trip (RK_SWEEP_QUEUED=0:
   // the readback after each axis' third sweep); whether either axis was left
   // open comes back with the roots' first readback (the two axes' pending
-  // counters; with RK_ROOTS_FUSED=0 a flag per axis in ctrl[10], ctrl[11],
+  // counters; with RK_ROOTS_FUSED=0 a flag per axis in CW_OPEN_X, CW_OPEN_Y,
   // which the first jumping round checks), and a pair left open repeats its
   // axes the careful way (no input of the BASELINE configs needs more than
   // three sweeps an axis)
@@ -682,8 +682,8 @@ int classify_narrow(rk_ctx *ctx, const rk_frags_soa *in, const rk_params *prms, 
     if (q > 0 || attempt > 0) HIPCHK(ctx, hipMemsetAsync(w.cx.state, rk::ST_UNKNOWN, m, st));
     // (the open flags and the counters: zero from the call's start for the first pair)
     if (queued && q > 0)
-      rk::zero_regions(st, {{w.ctrl + 10, 2 * sizeof(uint32_t)},
-                            {w.ctrl + 64, 2 * rk::PEND_WORDS * sizeof(uint32_t)}});
+      rk::zero_regions(st, {{w.ctrl + rk::CW_OPEN_X, 2 * sizeof(uint32_t)},
+                            {w.ctrl + rk::CW_PEND_X, 2 * rk::PEND_WORDS * sizeof(uint32_t)}});
     if (prof) mark(ctx, RK_PH_SWEEP_X);
     // X decisions: hits' parents (X winner); the X states become a bitmask after
     rk::Axis ax{w.cx.key, w.cx.ent, nullptr, nullptr, w.cx.state, nullptr, w.par,
@@ -691,7 +691,7 @@ int classify_narrow(rk_ctx *ctx, const rk_frags_soa *in, const rk_params *prms, 
                 pq.pos_ratio};
     uint32_t sweeps = blind;
     if ((rc = queued ? rk::resolve_axis_queued(ctx, ax, sc, blind,
-                                               fused_roots ? nullptr : w.ctrl + 10, junk)
+                                               fused_roots ? nullptr : w.ctrl + rk::CW_OPEN_X, junk)
                      : rk::resolve_axis(ctx, ax, sc, true, &sweeps)))
       return rc;
     ctx->stats.x_sweeps = sweeps;
@@ -719,7 +719,7 @@ int classify_narrow(rk_ctx *ctx, const rk_frags_soa *in, const rk_params *prms, 
     ay.par_dev = true;
     sweeps = blind;
     if ((rc = queued ? rk::resolve_axis_queued(ctx, ay, scy, blind,
-                                               fused_roots ? nullptr : w.ctrl + 11, junk)
+                                               fused_roots ? nullptr : w.ctrl + rk::CW_OPEN_Y, junk)
                      : rk::resolve_axis(ctx, ay, sc, true, &sweeps)))
       return rc;
     ctx->stats.y_sweeps = sweeps;
@@ -733,52 +733,54 @@ int classify_narrow(rk_ctx *ctx, const rk_frags_soa *in, const rk_params *prms, 
     bool open_axes = false;
     if (fused_roots) {
       // the new-group ranks from the parents' root flags (G straight into
-      // ctrl[32]); the wide-key flag, G and the queued axes' pending counters
+      // CW_GROUPS); the wide-key flag, G and the queued axes' pending counters
       // back in one readback; later pairs' member histograms and listed-chain
       // count cleared first
       rk::zero_regions(st, {{q > 0 ? w.ehist : nullptr, 4096 * sizeof(uint32_t)},
-                            {q > 0 ? w.ctrl + 12 : nullptr, sizeof(uint32_t)}});
+                            {q > 0 ? w.ctrl + rk::CW_CHAINS : nullptr, sizeof(uint32_t)}});
       // (each root's rank into its own parent word: a pair that repeats, a
       // later pair and a later call rewrite every parent word in their sweeps
       // before anything reads one)
-      rk::scan_root_ranks(w.par, m, ss, st, w.ctrl + 32);
-      if ((rc = readback(ctx, w.ctrl + 5, 64 - 5 + 2 * rk::PEND_WORDS))) return rc;
+      rk::scan_root_ranks(w.par, m, ss, st, w.ctrl + rk::CW_GROUPS);
+      if ((rc = readback(ctx, w.ctrl + rk::RB_ROOTS, rk::RB_ROOTS_N))) return rc;
       uint32_t pending = 0;
-      for (uint32_t k = 0; k < 2 * rk::PEND_WORDS; ++k) pending |= ctx->host[64 - 5 + k];
+      for (uint32_t k = 0; k < 2 * rk::PEND_WORDS; ++k)
+        pending |= ctx->host[rk::CW_PEND_X - rk::RB_ROOTS + k];
       if (queued && pending) {
         open_axes = true;  // an axis was left open: this pair again, the careful way
       } else {
-        G = ctx->host[27];
-        narrow_keys = ctx->host[1] == 0;
+        G = ctx->host[rk::CW_GROUPS - rk::RB_ROOTS];
+        narrow_keys = ctx->host[rk::CW_WIDE_KEYS - rk::RB_ROOTS] == 0;
         rounds = 1;
       }
     } else {
     // (the first round's changed-count with the scan's end word, one launch;
     // later pairs' member histograms too -- the first pair's are still zero)
     rk::zero_regions(st, {{w.isnew + m, sizeof(uint32_t)},
-                          {w.ctrl + 5, sizeof(uint32_t)},
+                          {w.ctrl + rk::CW_JUMP, sizeof(uint32_t)},
                           {q > 0 ? w.ehist : nullptr, 4096 * sizeof(uint32_t)}});
     for (;;) {
-      if (rounds > 0) HIPCHK(ctx, hipMemsetAsync(w.ctrl + 5, 0, sizeof(uint32_t), st));
-      rk::jump_round(pr, m, w.ctrl + 5, rounds == 0 ? w.isnew : nullptr, w.ctrl, st,
-                     queued && rounds == 0 ? w.ctrl + 10 : nullptr);
+      if (rounds > 0) HIPCHK(ctx, hipMemsetAsync(w.ctrl + rk::CW_JUMP, 0, sizeof(uint32_t), st));
+      rk::jump_round(pr, m, w.ctrl + rk::CW_JUMP, rounds == 0 ? w.isnew : nullptr, w.ctrl, st,
+                     queued && rounds == 0 ? w.ctrl + rk::CW_OPEN_X : nullptr);
       if (rounds == 0) {
         // the new-group flags are final after the first round: their scan
-        // (the group count G, in ctrl[32]) shares the round's readback
+        // (the group count G, in CW_GROUPS) shares the round's readback
         rk::exclusive_scan_u32(w.isnew, w.newrank, (size_t)m + 1, ss, st);
-        HIPCHK(ctx, hipMemcpyAsync(w.ctrl + 32, w.newrank + m, sizeof(uint32_t),
+        HIPCHK(ctx, hipMemcpyAsync(w.ctrl + rk::CW_GROUPS, w.newrank + m, sizeof(uint32_t),
                                    hipMemcpyDeviceToDevice, st));
       }
       // + the wide-key flag, the queued axes' open flags, G
-      if ((rc = readback(ctx, w.ctrl + 5, 28))) return rc;
-      if (rounds == 0 && queued && (ctx->host[5] || ctx->host[6])) {
+      if ((rc = readback(ctx, w.ctrl + rk::RB_ROUND, rk::RB_ROUND_N))) return rc;
+      if (rounds == 0 && queued && (ctx->host[rk::CW_OPEN_X - rk::RB_ROUND] ||
+                                    ctx->host[rk::CW_OPEN_Y - rk::RB_ROUND])) {
         open_axes = true;  // an axis was left open: this pair again, the careful way
         break;
       }
-      if (rounds == 0) G = ctx->host[27];
+      if (rounds == 0) G = ctx->host[rk::CW_GROUPS - rk::RB_ROUND];
       ++rounds;
-      narrow_keys = ctx->host[1] == 0;
-      if (!ctx->host[0]) break;
+      narrow_keys = ctx->host[rk::CW_WIDE_KEYS - rk::RB_ROUND] == 0;
+      if (!ctx->host[rk::CW_JUMP - rk::RB_ROUND]) break;
       if (rounds > 64) {
         ctx->err = "pointer jumping did not converge";
         return RK_E_INTERNAL;
@@ -841,11 +843,11 @@ int classify_narrow(rk_ctx *ctx, const rk_frags_soa *in, const rk_params *prms, 
     }
     if (prof) mark(ctx, RK_PH_GROUP_SORT);
     // one pair: the depth-limit heap segments' count (crafted inputs only)
-    // comes back with the final status word (ctrl[33]) instead of a wait of
+    // comes back with the final status word (CW_HEAPS) instead of a wait of
     // its own (several pairs share the scratch: each waits)
     if ((rc = rk::sort_groups_exact(sgid, w.goff, G, m, w.reckey, w.tag, w.otag, w.gsort, ss,
-                                    ctx->host + 128, narrow_keys, st, st2, ctx->fork, ctx->join,
-                                    npairs == 1 ? w.ctrl + 33 : nullptr,
+                                    ctx->host + rk::HOST_SCRATCH, narrow_keys, st, st2, ctx->fork,
+                                    ctx->join, npairs == 1 ? w.ctrl + rk::CW_HEAPS : nullptr,
                                     emit_direct ? &de : nullptr))) {
       ctx->err = "depth-limit heap segments: buffer allocation failed";
       return rc;
@@ -858,15 +860,18 @@ int classify_narrow(rk_ctx *ctx, const rk_frags_soa *in, const rk_params *prms, 
     if (prof) mark(ctx, RK_N_PHASES);
   }
   HIPCHK(ctx, hipEventRecord(ctx->ev1, st));
-  if ((rc = readback(ctx, w.ctrl, npairs == 1 ? 34 : 14))) return rc;
-  if (fused_roots && ctx->host[13]) {  // a parent chain above 4128 steps: round by round
+  if ((rc = readback(ctx, w.ctrl + rk::RB_END, npairs == 1 ? rk::RB_END1_N : rk::RB_END_N)))
+    return rc;
+  // a parent chain above 4128 steps: round by round
+  if (fused_roots && ctx->host[rk::CW_CHAIN_OPEN - rk::RB_END]) {
     collect_phases(ctx);
     return classify_narrow(ctx, in, prms, npairs, outs, pl, fallback, wire, false);
   }
-  if (npairs == 1 && m && ctx->host[33]) {  // heap segments: sorted now, then the result again
+  const uint32_t nheap = npairs == 1 && m ? ctx->host[rk::CW_HEAPS - rk::RB_END] : 0u;
+  if (nheap) {  // heap segments: sorted now, then the result again
     const uint32_t G = outs[0].n_groups;
-    if ((rc = rk::sort_groups_heap_deferred(G, m, w.reckey, w.tag, w.otag, w.gsort, ctx->host[33],
-                                            ctx->host + 128, st))) {
+    if ((rc = rk::sort_groups_heap_deferred(G, m, w.reckey, w.tag, w.otag, w.gsort, nheap,
+                                            ctx->host + rk::HOST_SCRATCH, st))) {
       ctx->err = "depth-limit heap segments: buffer allocation failed";
       return rc;
     }
@@ -878,10 +883,10 @@ int classify_narrow(rk_ctx *ctx, const rk_frags_soa *in, const rk_params *prms, 
                       outs[0].out_order, st);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipEventRecord(ctx->ev1, st));
-    if ((rc = readback(ctx, w.ctrl, 1))) return rc;
+    if ((rc = readback(ctx, w.ctrl + rk::CW_ERR, 1))) return rc;
   }
   collect_phases(ctx);
-  if ((rc = err_status(ctx, ctx->host[0]))) return rc;
+  if ((rc = err_status(ctx, ctx->host[rk::CW_ERR - rk::RB_END]))) return rc;
   float ms = 0;
   HIPCHK(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
   ctx->stats.device_ms = ms;
@@ -972,20 +977,22 @@ int classify_device(rk_ctx *ctx, const rk_frags_soa *in, const rk_params *prms, 
   ctx->stats.n_in = n;
 
   HIPCHK(ctx, hipEventRecord(ctx->ev0, st));
-  HIPCHK(ctx, hipMemsetAsync(w.ctrl, 0, (64 + rk::PEND_WORDS) * sizeof(uint32_t), st));
+  HIPCHK(ctx, hipMemsetAsync(w.ctrl, 0, rk::CW_GENERIC_WORDS * sizeof(uint32_t), st));
   rk::Frags f{in->x_start, in->y_start, in->length, in->strand, n};
   mark(ctx, RK_PH_PREP);
 
   // 1-2: processing order = stable sort of rows by xStart/10 (dropped bucket last)
-  rk::prep_keys(f, pl.vsize, pl.max_x, pl.max_y, w.pkey_in, w.p.rec, w.ctrl + 1, w.ctrl, st);
+  rk::prep_keys(f, pl.vsize, pl.max_x, pl.max_y, w.pkey_in, w.p.rec,
+                w.ctrl + rk::CW_KEPT, w.ctrl + rk::CW_ERR, st);
   mark(ctx, RK_PH_ORDER);
   rk::radix_sort_pairs(w.pkey_in, nullptr, w.p.pkey, w.p.row, w.tk, w.tv, n,
                        rk::bit_length(pl.vsize - 1), w.radix, w.radix_words, st);
   HIPCHK(ctx, hipGetLastError());
-  if ((rc = readback(ctx, w.ctrl, 2))) return rc;
-  if ((rc = err_status(ctx, ctx->host[0]))) return rc;
-  const bool fast32 = !(ctx->host[0] & rk::ERRB_WIDE_LENGTH);
-  const uint32_t m = ctx->host[1];
+  if ((rc = readback(ctx, w.ctrl + rk::RB_PREP, rk::RB_PREP_N))) return rc;
+  const uint32_t ebits = ctx->host[rk::CW_ERR - rk::RB_PREP];
+  if ((rc = err_status(ctx, ebits))) return rc;
+  const bool fast32 = !(ebits & rk::ERRB_WIDE_LENGTH);
+  const uint32_t m = ctx->host[rk::CW_KEPT - rk::RB_PREP];
   ctx->stats.n_proc = m;
   for (uint32_t q = 0; q < npairs; ++q) outs[q].n_out = m, outs[q].n_groups = 0;
   if (m == 0) {
@@ -1008,7 +1015,7 @@ int classify_device(rk_ctx *ctx, const rk_frags_soa *in, const rk_params *prms, 
   HIPCHK(ctx, hipStreamWaitEvent(ctx->stream2, ctx->fork, 0));
   rk::radix_sort_pairs(w.p.keyy, nullptr, w.cy.key, w.cy.ent, w.tk2, w.tv2, m,
                        rk::bit_length(2ull * pl.nby - 1), w.radix2, w.radix_words, ctx->stream2);
-  rk::sort_keys(w.p, m, w.ctrl + 6, ctx->stream2);
+  rk::sort_keys(w.p, m, w.ctrl + rk::CW_WIDE_KEYS, ctx->stream2);
   HIPCHK(ctx, hipEventRecord(ctx->join, ctx->stream2));
   mark(ctx, RK_PH_OCC_CSR);
   rk::radix_sort_pairs(w.p.keyx, nullptr, w.cx.key, w.cx.ent, w.tk, w.tv, m,
@@ -1048,21 +1055,22 @@ int classify_device(rk_ctx *ctx, const rk_frags_soa *in, const rk_params *prms, 
     HIPCHK(ctx, hipMemsetAsync(w.isnew + m, 0, sizeof(uint32_t), st));
     uint32_t rounds = 0;
     for (;;) {
-      HIPCHK(ctx, hipMemsetAsync(w.ctrl + 5, 0, sizeof(uint32_t), st));
-      rk::jump_round(w.p, m, w.ctrl + 5, rounds == 0 ? w.isnew : nullptr, w.ctrl, st);
-      if ((rc = readback(ctx, w.ctrl + 5, 2))) return rc;  // + the wide-key flag
+      HIPCHK(ctx, hipMemsetAsync(w.ctrl + rk::CW_JUMP, 0, sizeof(uint32_t), st));
+      rk::jump_round(w.p, m, w.ctrl + rk::CW_JUMP, rounds == 0 ? w.isnew : nullptr, w.ctrl, st);
+      // + the wide-key flag
+      if ((rc = readback(ctx, w.ctrl + rk::RB_GROUND, rk::RB_GROUND_N))) return rc;
       ++rounds;
-      if (!ctx->host[0]) break;
+      if (!ctx->host[rk::CW_JUMP - rk::RB_GROUND]) break;
       if (rounds > 64) {
         ctx->err = "pointer jumping did not converge";
         return RK_E_INTERNAL;
       }
     }
     ctx->stats.jump_rounds = rounds;
-    const bool narrow_keys = ctx->host[1] == 0;
+    const bool narrow_keys = ctx->host[rk::CW_WIDE_KEYS - rk::RB_GROUND] == 0;
     rk::exclusive_scan_u32(w.isnew, w.newrank, (size_t)m + 1, ss, st);
     if ((rc = readback(ctx, w.newrank + m, 1))) return rc;
-    const uint32_t G = ctx->host[0];
+    const uint32_t G = *ctx->host;
     out->n_groups = G;
     ctx->stats.n_groups = G;
     rk::assign_gid(w.p, m, w.newrank, st);
@@ -1075,8 +1083,8 @@ int classify_device(rk_ctx *ctx, const rk_frags_soa *in, const rk_params *prms, 
     rk::build_records(w.gmem, w.p.hrec, m, w.reckey, w.tag, st);
     if (prof) mark(ctx, RK_PH_GROUP_SORT);
     if ((rc = rk::sort_groups_exact(w.sgid, w.goff, G, m, w.reckey, w.tag, w.otag, w.gsort, ss,
-                                    ctx->host + 128, narrow_keys, st, ctx->stream2, ctx->fork,
-                                    ctx->join))) {
+                                    ctx->host + rk::HOST_SCRATCH, narrow_keys, st, ctx->stream2,
+                                    ctx->fork, ctx->join))) {
       ctx->err = "depth-limit heap segments: buffer allocation failed";
       return rc;
     }
@@ -1087,9 +1095,9 @@ int classify_device(rk_ctx *ctx, const rk_frags_soa *in, const rk_params *prms, 
     if (prof) mark(ctx, RK_N_PHASES);
   }
   HIPCHK(ctx, hipEventRecord(ctx->ev1, st));
-  if ((rc = readback(ctx, w.ctrl, 1))) return rc;
+  if ((rc = readback(ctx, w.ctrl + rk::CW_ERR, 1))) return rc;
   collect_phases(ctx);
-  if ((rc = err_status(ctx, ctx->host[0]))) return rc;
+  if ((rc = err_status(ctx, *ctx->host))) return rc;
   float ms = 0;
   HIPCHK(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
   ctx->stats.device_ms = ms;
@@ -1136,7 +1144,8 @@ extern "C" int rk_create(rk_ctx **out, int device) {
       hipEventCreateWithFlags(&ctx->fork, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&ctx->join, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&ctx->aux, hipEventDisableTiming) != hipSuccess ||
-      hipHostMalloc((void **)&ctx->host, 256 * sizeof(uint32_t), hipHostMallocDefault) !=
+      hipHostMalloc((void **)&ctx->host, rk::HOST_WORDS * sizeof(uint32_t),
+                    hipHostMallocDefault) !=
           hipSuccess) {
     rk_destroy(ctx);
     return RK_E_HIP;
@@ -1314,7 +1323,7 @@ extern "C" int rk_std_sort_segments(rk_ctx *ctx, const uint64_t *keys, uint64_t 
     // one-element segments are not written by the group sort: their slot stays
     (void)hipMemcpyAsync(dot, dt, M * 4, hipMemcpyDeviceToDevice, st);
     rc = rk::sort_groups_exact(dg, doff, nseg, m, dk, dt, dot, dgs, rk::ScanScratch{dsc, sc},
-                               ctx->host + 128, narrow, st);
+                               ctx->host + rk::HOST_SCRATCH, narrow, st);
     if (!rc && (hipGetLastError() != hipSuccess ||
                 hipMemcpyAsync(perm, dot, M * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
                 hipStreamSynchronize(st) != hipSuccess))

@@ -479,7 +479,7 @@ int write_device(rk_ctx *ctx, const rk_db *db, const char *path, const rk_result
   }
   HIPCHK(ctx, hipMemcpyAsync(ctx->host, S.perr, 4, hipMemcpyDeviceToHost, s));
   HIPCHK(ctx, hipStreamSynchronize(s));
-  if (ctx->host[0]) {
+  if (*ctx->host) {  // (the put pass' own error word, not a control block's)
     ctx->err = "csv put pass: a block's text does not fit its place";
     return finish(RK_E_INTERNAL);
   }

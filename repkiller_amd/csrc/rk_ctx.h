@@ -50,7 +50,7 @@ struct rk_ctx {
   size_t ws_nw_cap = 0;
   void *nw_small = nullptr;  // its control words + digit histograms: allocated once, so
                              // the pack check runs before the workspace is sized
-  uint32_t *host = nullptr;  // pinned readback words
+  uint32_t *host = nullptr;  // pinned readback words (HOST_WORDS, rk_ctrl.h)
   // device copies for rk_classify (host-buffer entry point)
   void *io = nullptr;
   size_t io_cap = 0;
@@ -170,7 +170,7 @@ int dev_alloc(rk_ctx *ctx, void **p, size_t bytes, const char *what);
 int grow(rk_ctx *ctx, void **buf, size_t *cap, size_t need, const char *what);
 double wall_ms();
 
-// copy `count` device words into ctx->host and wait
+// copy `count` (<= HOST_WORDS) device words into ctx->host and wait
 int readback(rk_ctx *ctx, const uint32_t *dev, uint32_t count);
 // fold the launches timed during the current call into the per-kernel totals
 void collect_kernel_timing(rk_ctx *ctx);

@@ -2482,30 +2482,51 @@ size_t lds_bytes(uint32_t cap, size_t key_bytes, uint32_t reg_max) {
          (lds_stack(cap) + (reg_max ? 2 : 1) * nfr) * sizeof(Frame) + 16;
 }
 
+// The group sort's scratch, laid out for m members in ngroups groups (every
+// tier is listed; nblk blocks of TCH groups count them).  A later call on the
+// same scratch with the same (m, ngroups) finds the last sort's lists and heap
+// queue again.
+struct GsScratch {
+  uint32_t nblk;
+  uint32_t *pl, *pr;   // m words each: stopper lists; segment heads
+  uint32_t *list;      // ngroups + 1 words: the tier lists
+  uint8_t *bnd;        // m bytes: segment bounds (16-B aligned)
+  uint32_t *bc, *boff; // NTIER * nblk + 1 words each: block counts and their scan
+  uint32_t *bm;        // NTIER * nblk words: block members (timing)
+  HeapSeg *heapq;      // HEAPQ_CAP segments
+  uint32_t *heapq_n;   // their count and the two claim counters
+
+  template <class T>
+  static T *aligned(void *p, uintptr_t a) {
+    return reinterpret_cast<T *>((reinterpret_cast<uintptr_t>(p) + a - 1) & ~(a - 1));
+  }
+  GsScratch(void *scratch, uint32_t m, uint32_t ngroups) : nblk((ngroups + TCH - 1) / TCH) {
+    const size_t nb = (size_t)NTIER * nblk;
+    pl = reinterpret_cast<uint32_t *>(scratch);
+    pr = pl + m;
+    list = pr + m;
+    bnd = aligned<uint8_t>(list + ngroups + 1, 16);
+    bc = aligned<uint32_t>(bnd + m, 64);
+    boff = bc + nb + 1;
+    bm = boff + nb + 1;
+    heapq = aligned<HeapSeg>(bm + nb, 64);
+    heapq_n = reinterpret_cast<uint32_t *>(heapq + HEAPQ_CAP);
+  }
+  TierLists tiers() const { return TierLists{list, boff, nblk}; }
+  // What a caller allocates (256-B aligned): the arrays above, a block of
+  // counts to spare and ~700 bytes for the three alignment gaps -- at least
+  // 584 bytes more than the layout's end.
+  static size_t bytes(uint32_t m, uint32_t ngroups) {
+    const size_t nb = ((size_t)ngroups / TCH + 1) * NTIER;
+    return (size_t)m * 4 * 2 + ((size_t)ngroups + 1) * 4 + (size_t)m + 128 + (nb + 1) * 4 * 2 +
+           nb * 4 + 256 + 256 + (HEAPQ_CAP + 1) * sizeof(HeapSeg) + 64;
+  }
+};
+
 }  // namespace
 
-size_t groupsort_scratch_bytes(uint32_t n) {
-  const size_t nblk = (size_t)n / TCH + 1;
-  // pl, pr (stopper lists; segment heads); tier lists; bounds; block counts
-  // (+ scan), block members
-  return (size_t)n * 4 * 2 + ((size_t)n + 1) * 4 + (size_t)n + 128 +
-         (nblk * NTIER + 1) * 4 * 2 + nblk * NTIER * 4 + 256 + 256 +
-         (HEAPQ_CAP + 1) * sizeof(HeapSeg) + 64;
-}
-
-// the heap-segment queue inside sort_groups_exact's scratch (the layout below)
-static HeapSeg *heap_queue(void *scratch, uint32_t m, uint32_t ngroups) {
-  const uint32_t nblk = (ngroups + TCH - 1) / TCH;
-  uint32_t *pl = reinterpret_cast<uint32_t *>(scratch);
-  uint32_t *list = pl + 2 * (size_t)m;
-  uint8_t *bnd = reinterpret_cast<uint8_t *>(
-      (reinterpret_cast<uintptr_t>(list + ngroups + 1) + 15) & ~(uintptr_t)15);
-  uint32_t *bc = reinterpret_cast<uint32_t *>(
-      (reinterpret_cast<uintptr_t>(bnd + m) + 63) & ~(uintptr_t)63);
-  uint32_t *bm = bc + 2 * ((size_t)NTIER * nblk + 1);
-  return reinterpret_cast<HeapSeg *>(
-      (reinterpret_cast<uintptr_t>(bm + (size_t)NTIER * nblk) + 63) & ~(uintptr_t)63);
-}
+// (a scratch for up to n members in up to n groups)
+size_t groupsort_scratch_bytes(uint32_t n) { return GsScratch::bytes(n, n); }
 
 // The heap segments of a sort_groups_exact call made with `heap_count`: their
 // number was copied to heap_count, which the caller read back together with
@@ -2515,22 +2536,15 @@ int sort_groups_heap_deferred(uint32_t ngroups, uint32_t m, uint64_t *key, uint3
                               uint32_t *host_words, hipStream_t st) {
   nheap = nheap < HEAPQ_CAP ? nheap : HEAPQ_CAP;
   if (!nheap) return RK_OK;
-  return heap_segments(heap_queue(scratch, m, ngroups), nheap, key, tag, otag, host_words, st);
+  return heap_segments(GsScratch(scratch, m, ngroups).heapq, nheap, key, tag, otag, host_words,
+                       st);
 }
 
 void emit_large_groups(uint32_t ngroups, uint32_t m, const uint32_t *goff, const uint32_t *otag,
                        const void *scratch, DirectEmit direct, hipStream_t st) {
   if (!m) return;
-  // (sort_groups_exact's layout: the lists after pl and pr, the scanned block
-  // counts after the counts)
-  const uint32_t nblk = (ngroups + TCH - 1) / TCH;
-  const uint32_t *list = reinterpret_cast<const uint32_t *>(scratch) + 2 * (size_t)m;
-  const uint8_t *bnd = reinterpret_cast<const uint8_t *>(
-      (reinterpret_cast<uintptr_t>(list + ngroups + 1) + 15) & ~(uintptr_t)15);
-  const uint32_t *bc = reinterpret_cast<const uint32_t *>(
-      (reinterpret_cast<uintptr_t>(bnd + m) + 63) & ~(uintptr_t)63);
-  const uint32_t *boff = bc + (size_t)NTIER * nblk + 1;
-  k_emit_listed<<<1024, 256, 0, st>>>(TierLists{list, boff, nblk}, NTIER - 1, goff, otag, direct, m);
+  const GsScratch gs(const_cast<void *>(scratch), m, ngroups);  // (the lists are only read)
+  k_emit_listed<<<1024, 256, 0, st>>>(gs.tiers(), NTIER - 1, goff, otag, direct, m);
 }
 
 int sort_groups_exact(const uint32_t *gid_sorted, const uint32_t *goff, uint32_t ngroups,
@@ -2543,32 +2557,25 @@ int sort_groups_exact(const uint32_t *gid_sorted, const uint32_t *goff, uint32_t
     return RK_OK;
   }
   int hrc = RK_OK;  // the heap segments' status (sorted here only without heap_count)
-  constexpr int NL = NTIER;  // every tier is listed
   // groups of <= 64 members (k_sort_small, registers) run on `side`,
   // concurrently with the LDS tiers
   hipStream_t s2 = side ? side : st;
   constexpr Caps caps = lds_caps();
-  const uint32_t nblk = (ngroups + TCH - 1) / TCH;
-  uint32_t *pl = reinterpret_cast<uint32_t *>(scratch);
-  uint32_t *pr = pl + m;
-  uint32_t *list = pr + m;
-  uint8_t *bnd = reinterpret_cast<uint8_t *>(
-      (reinterpret_cast<uintptr_t>(list + ngroups + 1) + 15) & ~(uintptr_t)15);
-  uint32_t *bc = reinterpret_cast<uint32_t *>(
-      (reinterpret_cast<uintptr_t>(bnd + m) + 63) & ~(uintptr_t)63);
-  uint32_t *boff = bc + (size_t)NL * nblk + 1;
-  uint32_t *bm = boff + (size_t)NL * nblk + 1;
-  HeapSeg *heapq = heap_queue(scratch, m, ngroups);  // (after bm's NL * nblk words)
-  uint32_t *heapq_n = reinterpret_cast<uint32_t *>(heapq + HEAPQ_CAP);
+  const GsScratch gs(scratch, m, ngroups);
+  const uint32_t nblk = gs.nblk;
+  uint32_t *const pl = gs.pl, *const pr = gs.pr, *const list = gs.list, *const bc = gs.bc,
+                 *const boff = gs.boff, *const bm = gs.bm, *const heapq_n = gs.heapq_n;
+  uint8_t *const bnd = gs.bnd;
+  HeapSeg *const heapq = gs.heapq;
   const bool timing = g_ktimer != nullptr;
   if (timing) {
     g_ktimer->tier_nblk = nblk;
     for (int u = 0; u < KernelTimer::TIERS; ++u) g_ktimer->tier_slot[u] = -1;
   }
   k_tier_count<<<nblk, 256, 0, st>>>(goff, ngroups, nblk, bc, timing ? bm : nullptr, heapq_n);
-  exclusive_scan_u32(bc, boff, (size_t)NL * nblk + 1, ss, st);
+  exclusive_scan_u32(bc, boff, (size_t)NTIER * nblk + 1, ss, st);
   k_tier_lists<<<nblk, 256, 0, st>>>(goff, ngroups, nblk, boff, list, bnd, m);
-  const TierLists tl{list, boff, nblk};
+  const TierLists tl = gs.tiers();
   // algorithmic bytes of every tier (timing only): each member's key read, its
   // tag (its position) written once at its final slot -- 12 B x the tier's members
   // (16 B with the direct emit: the tag's row read and written instead),

@@ -10,6 +10,7 @@
 #include <stdint.h>
 
 #include "../../include/repkiller_amd.h"
+#include "rk_ctrl.h"
 
 namespace rk {
 
@@ -21,7 +22,7 @@ enum : uint8_t {
   ST_HIT = 3,          // hit on this axis; winner final
 };
 
-// device error bits (ctrl[0])
+// device error bits (control word CW_ERR / SC_ERR, rk_ctrl.h)
 enum : uint32_t {
   ERRB_UB_BUCKET = 1u,
   ERRB_UB_CENTER = 2u,
@@ -183,9 +184,8 @@ size_t runs_scratch_words(uint32_t m);
 void build_runs(const Axis &ax, RunList &rl, uint32_t *dev_count, uint32_t *host_words,
                 hipStream_t st);
 // One sweep.  rpend[p] (start p of a long run) = run still has undecided
-// entries; set to 1 before the first sweep.  counters: PEND_WORDS words, their
-// sum is the number of waves/runs still pending after the sweep.
-constexpr uint32_t PEND_WORDS = 64;
+// entries; set to 1 before the first sweep.  counters: PEND_WORDS words
+// (rk_ctrl.h), their sum is the number of waves/runs still pending after the sweep.
 void occupancy_sweep(const Axis &ax, const RunList &rl, uint8_t *rpend, uint32_t *counters,
                      bool first, hipStream_t st, bool clear = true);
 
@@ -285,7 +285,7 @@ size_t groupsort_scratch_bytes(uint32_t n);
 // Every record's tag is its position (tag[x] == x): the tiers compute it, and
 // `tag` is only the scratch array in which the groups above 2048 members move
 // their tags (written there first), so callers need not fill it.
-// gid_sorted: group id of every record; host_words: >= 16 pinned words;
+// gid_sorted: group id of every record; host_words: GS_HOST_WORDS pinned words;
 // narrow_keys: every key fits 32 bits (LDS tiers stage 4-byte keys).
 // side (optional): a second stream for the tiers of <= 64 members, forked
 // and joined through ev_fork / ev_join.
@@ -324,9 +324,8 @@ void emit_result(const uint32_t *otag, const uint32_t *sgid, const uint32_t *gof
 
 // -------------------------------------------------------- rk_narrow.hip --
 // The record-carrying pipeline (16-B records, one-sweep radix sorts, X axis by
-// chunks of the processing order).  ctrl words: [0] error bits, [1] kept rows,
-// [3] not representable, [4] longest length, [6] wide sort keys, [8]
-// forward-strand kept rows.
+// chunks of the processing order).  ctrl: the record block's words (CW_*,
+// rk_ctrl.h).
 struct NwDigits {
   int passes;
   int shift[4], db[4];
@@ -475,9 +474,9 @@ void nw_fill_y(const uint32_t *ent, const uint32_t *bits, uint8_t *state, uint32
 void nw_assign(const uint32_t *par, const uint32_t *newrank, uint32_t *gidp, uint32_t m,
                const NwDigits &e, uint32_t *ehist, hipStream_t st);
 // the roots and gids in one pass after scan_root_ranks (the roots' parent
-// words hold ROOT_FLAG | rank, ctrl[32] the group count; list: m words of
-// scratch; ctrl[12] its count (zero on entry), ctrl[13] = 1 when a chain stayed open after
-// 4128 steps, ctrl[0] |= ERRB_INTERNAL on a parent after its child)
+// words hold ROOT_FLAG | rank, CW_GROUPS the group count; list: m words of
+// scratch; CW_CHAINS its count (zero on entry), CW_CHAIN_OPEN = 1 when a chain stayed
+// open after 4128 steps, CW_ERR |= ERRB_INTERNAL on a parent after its child)
 void nw_assign_jump(uint32_t *par, uint32_t *gidp, uint32_t m, const NwDigits &e,
                     uint32_t *ehist, uint32_t *list, uint32_t *ctrl, hipStream_t st);
 void nw_member_sort(const uint4 *erec, const uint32_t *gidp, uint4 *t0, uint4 *t1, uint32_t m,

@@ -896,8 +896,8 @@ struct DstMembers {
 // processing key (all passes) and of the Y axis key of every kept row, the
 // kept-row and forward-strand counts, the longest kept length, the
 // out-of-bounds checks (xStart/10 >= vsize; probes past an occupancy array)
-// and whether every row packs into a record.  ctrl: [0] error bits, [1] kept
-// rows, [3] some row does not pack, [4] longest kept length, [8] forward kept.
+// and whether every row packs into a record (ctrl: CW_ERR, CW_KEPT, CW_NOPACK,
+// CW_MAXLEN, CW_FWD_KEPT).
 template <class Rows>
 struct OrderHistArgs {
   Rows rows;
@@ -954,12 +954,12 @@ __global__ void __launch_bounds__(256) k_nw_order_hist(OrderHistArgs<Rows> a) {
   hist_flush(L, a.D, a.ghist);
   hist_flush(LY, a.yd, a.yhist);
   if (threadIdx.x == 0) {
-    if (red[0]) atomicAdd(&a.ctrl[1], red[0]);
-    if (red[1]) atomicAdd(&a.ctrl[8], red[1]);
-    if (red[2]) atomicMax(&a.ctrl[4], red[2]);
-    if (red[3] & 1u) atomicOr(&a.ctrl[0], ERRB_UB_BUCKET);
-    if (red[3] & 2u) atomicOr(&a.ctrl[0], ERRB_UB_CENTER);
-    if (red[3] & 4u) atomicOr(&a.ctrl[3], 1u);
+    if (red[0]) atomicAdd(&a.ctrl[CW_KEPT], red[0]);
+    if (red[1]) atomicAdd(&a.ctrl[CW_FWD_KEPT], red[1]);
+    if (red[2]) atomicMax(&a.ctrl[CW_MAXLEN], red[2]);
+    if (red[3] & 1u) atomicOr(&a.ctrl[CW_ERR], ERRB_UB_BUCKET);
+    if (red[3] & 2u) atomicOr(&a.ctrl[CW_ERR], ERRB_UB_CENTER);
+    if (red[3] & 4u) atomicOr(&a.ctrl[CW_NOPACK], 1u);
   }
 }
 
@@ -1048,7 +1048,7 @@ struct XChunkArgs {
   uint32_t *xpos;        // X position of every fragment (processing index)
   uint2 *erk;            // member records (processing order): {file row, sort key low 32}
   uint32_t *ehi;         // ... and the sort key's high 32 bits
-  uint32_t *ctrl;        // [6] some sort key >= 2^32
+  uint32_t *ctrl;        // CW_WIDE_KEYS: some sort key >= 2^32
 };
 
 __global__ void __launch_bounds__(64 * XC_WAVES) k_nw_xchunk(XChunkArgs a) {
@@ -1116,7 +1116,7 @@ __global__ void __launch_bounds__(64 * XC_WAVES) k_nw_xchunk(XChunkArgs a) {
       carry_end = __shfl(end_ys, 0);
     }
   }
-  if (__ballot(wide) && lane == 0) atomicOr(&a.ctrl[6], 1u);
+  if (__ballot(wide) && lane == 0) atomicOr(&a.ctrl[CW_WIDE_KEYS], 1u);
   // bin starts (exclusive scan over the 2W bins, W/32 per lane)
   {
     const uint32_t per = nb2 / 64;
@@ -1234,7 +1234,7 @@ __global__ void __launch_bounds__(256) k_nw_assign(const uint32_t *__restrict__ 
 // + the flag scan + k_nw_assign (their flag array written and read, the
 // parents read twice).
 //
-// Every gid written is below G (ctrl[32]), whatever the parents hold: each of
+// Every gid written is below G (CW_GROUPS), whatever the parents hold: each of
 // the G roots takes its own rank from its own word, so no group is empty and
 // the member sort and the group sort downstream stay in bounds even when a
 // chain is left open (*open: the caller then classifies again the
@@ -2239,12 +2239,12 @@ void nw_assign_jump(uint32_t *par, uint32_t *gidp, uint32_t m, const NwDigits &e
     return e ? std::max(1, atoi(e)) : 4096;
   }();
   kt_begin(st, KID_NW_ASSIGN);
-  k_nw_assign_jump<<<grid_for(m, 256, 2048), 256, 0, st>>>(par, ctrl + 32, gidp, m, to_digits(e),
-                                                           ehist, list, ctrl + 12, ctrl, steps1);
+  k_nw_assign_jump<<<grid_for(m, 256, 2048), 256, 0, st>>>(
+      par, ctrl + CW_GROUPS, gidp, m, to_digits(e), ehist, list, ctrl + CW_CHAINS, ctrl, steps1);
   // parent, the chain's flagged word, the rank back as the parent, gid
   kt_end(st, KID_NW_ASSIGN, 16.0 * m);
-  k_nw_assign_rest<<<256, 256, 0, st>>>(par, ctrl + 32, gidp, to_digits(e), ehist, list, ctrl + 12,
-                                        ctrl + 13, ctrl, steps2);
+  k_nw_assign_rest<<<256, 256, 0, st>>>(par, ctrl + CW_GROUPS, gidp, to_digits(e), ehist, list,
+                                        ctrl + CW_CHAINS, ctrl + CW_CHAIN_OPEN, ctrl, steps2);
 }
 
 void nw_assign(const uint32_t *par, const uint32_t *newrank, uint32_t *gidp, uint32_t m,

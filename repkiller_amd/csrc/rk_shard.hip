@@ -59,6 +59,7 @@ namespace rk {
 namespace {
 
 constexpr uint32_t MAXP = 32;
+static_assert(SC_TOTALS + MAXP + 1 <= SC_FAST, "the partition totals stop before the fast words");
 constexpr uint32_t NBINS = 4096;  // coarse histogram bins (LDS resident)
 
 #define GRID_STRIDE(i, n)                                                      \
@@ -578,7 +579,8 @@ __global__ void k_local_par(const uint32_t *par, uint32_t m, uint32_t poff, uint
     isroot[k] = pg == poff + k ? 1u : 0u;
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) isroot[m] = 0;
-  if (__ballot(link) && (threadIdx.x & 63) == 0) atomicOr(&err[23], 1u);  // a cross-slice link
+  // a cross-slice link
+  if (__ballot(link) && (threadIdx.x & 63) == 0) atomicOr(&err[SC_XLINK], 1u);
 }
 
 __global__ void k_init_labels(const uint32_t *lpar, const uint32_t *ext, const uint32_t *lrank,
@@ -701,9 +703,7 @@ struct Shard {
   hipStream_t st;   // compute + exchanges
   hipStream_t st2;  // overlapped work (Y bucket order, in-group sort keys)
   uint32_t P, me;
-  uint32_t *ctrl = nullptr;  // [0] err bits, [1] kept, [2] mismatches, [3] jump flag,
-                            // [4] long-run count, [6] wide keys, [64..128) sweep
-                            // counters, [128..161) partition totals
+  uint32_t *ctrl = nullptr;  // SC_WORDS control words (SC_*, rk_ctrl.h)
   uint64_t bytes_sent = 0;
   // elements every rank received in the last exchange (known to every rank
   // from that exchange's count all-gather: no further collective needed)
@@ -902,9 +902,9 @@ struct Shard {
     kt_end(st, KID_PART, 0.0);
     launched("k_part_count");
     exclusive_scan_u32(cnt, pp.off, len, scan_scratch(SL_PSCAN, len), st);
-    k_totals<<<1, 64, 0, st>>>(pp.off, pp.nblk, P, ctrl + 128);
+    k_totals<<<1, 64, 0, st>>>(pp.off, pp.nblk, P, ctrl + SC_TOTALS);
     launched("k_totals");
-    std::vector<uint32_t> t = d2h(ctrl + 128, P + 1);
+    std::vector<uint32_t> t = d2h(ctrl + SC_TOTALS, P + 1);
     for (uint32_t q = 0; q < P; ++q) pp.cnt[q] = t[q + 1] - t[q];
     pp.total = t[P];
   }
@@ -985,7 +985,7 @@ struct Shard {
   void emit(const Op &op, const PartPlan &pp) {
     kt_begin(st, KID_PART);
     k_part_scatter<<<pp.nblk, 256, 0, st>>>(op, pp.n, P, pp.nblk, pp.off, pp.mcache, pp.cap,
-                                            expect_flag ? expect_flag : ctrl + 7);
+                                            expect_flag ? expect_flag : ctrl + SC_EXPECT);
     kt_end(st, KID_PART, 0.0);
     launched("k_part_scatter");
   }
@@ -1327,7 +1327,7 @@ uint32_t sweep_axis(Shard &S, const AxisIn &a, const Csr &c, const rk_params &p)
           p.len_ratio, p.pos_ratio};
   SweepScratch sc{S.take<uint32_t>(SL_RUNS, runs_scratch_words(n)),
                   S.take<uint8_t>(SL_WPEND, n / 64 + 1), S.take<uint8_t>(SL_RPEND, n),
-                  S.ctrl + 64, S.ctrl + 4};
+                  S.ctrl + SC_PEND, S.ctrl + SC_SWEEP_COUNT};
   uint32_t sweeps = 0;
   S.check(resolve_axis(S.ctx, ax, sc, a.fast32, &sweeps));
   return sweeps;
@@ -1388,13 +1388,14 @@ void verify_y_halo(Shard &S, RelOp relop, const uint8_t *ycode, uint8_t *ystate,
       ctx->err = "Y halo state count mismatch";
       throw RK_E_INTERNAL;
     }
-    S.zero(S.ctrl + 2, 4);
+    S.zero(S.ctrl + SC_MISMATCH, 4);
     if (nrel) {
       k_cmp_y<<<grid_for(nrel, 256, 1024), 256, 0, S.st>>>(relidx, nrel, yused, rys,
-                                                            S.ctrl + 2);
+                                                            S.ctrl + SC_MISMATCH);
       S.launched("k_cmp_y");
     }
-    const uint32_t mism = nrel ? S.read1(S.ctrl + 2) : 0u;  // no relevant halo: nothing to compare
+    // no relevant halo: nothing to compare
+    const uint32_t mism = nrel ? S.read1(S.ctrl + SC_MISMATCH) : 0u;
     if (S.sum_any(mism) == 0) break;
     if (mism) {
       ++ss.y_reruns;
@@ -1523,16 +1524,16 @@ const uint32_t *resolve_roots(Shard &S, uint32_t *xg, const ParRec *prr, uint32_
         ctx->err = "pointer jumping did not converge";
         throw RK_E_INTERNAL;
       }
-      S.zero(S.ctrl + 3, 4);
-      jump_round(jp, m, S.ctrl + 3, rounds == 0 ? isnew : nullptr, S.ctrl, S.st);
+      S.zero(S.ctrl + SC_JUMP, 4);
+      jump_round(jp, m, S.ctrl + SC_JUMP, rounds == 0 ? isnew : nullptr, S.ctrl, S.st);
       S.launched("jump_round");
-      if (!S.read1(S.ctrl + 3)) break;
+      if (!S.read1(S.ctrl + SC_JUMP)) break;
     }
   });
   // the error bits, the root count and the cross-slice link flag: one readback
   uint32_t nroots = 0, xlink = 0, ebits = 0;
   if (m) {
-    const std::vector<uint32_t> w = S.d2h_words({S.ctrl, lrank + m, S.ctrl + 23});
+    const std::vector<uint32_t> w = S.d2h_words({S.ctrl + SC_ERR, lrank + m, S.ctrl + SC_XLINK});
     ebits = w[0];
     nroots = w[1];
     xlink = w[2];
@@ -1648,8 +1649,8 @@ int classify_sharded_impl(Shard &S, const rk_frags_soa *in, const rk_params *prm
   }
   if (!rc) {
     try {
-      S.ctrl = S.take<uint32_t>(SL_CTRL, 256);
-      S.zero(S.ctrl, 256 * 4);
+      S.ctrl = S.take<uint32_t>(SL_CTRL, SC_WORDS);
+      S.zero(S.ctrl, SC_WORDS * 4);
     } catch (int code) {
       rc = code;
     }
@@ -1686,7 +1687,7 @@ int classify_sharded_impl(Shard &S, const rk_frags_soa *in, const rk_params *prm
       // (with as many queued sweeps next time as it took)
       std::memset(ctx->sh_fp, 0, sizeof ctx->sh_fp);
       ss.fast_retry = 1;
-      S.zero(S.ctrl, 256 * 4);
+      S.zero(S.ctrl, SC_WORDS * 4);
       r = classify_sharded_nw(S, geo, in, p, one_on, y_early, row_base, out, t0);
       for (int a = 0; a < 2; ++a)
         ctx->sh_blind[a] = S.max_sweeps[a] > 3 ? S.max_sweeps[a] : 3u;
@@ -1697,7 +1698,7 @@ int classify_sharded_impl(Shard &S, const rk_frags_soa *in, const rk_params *prm
       return r;
     }
     std::memset(ctx->sh_fp, 0, sizeof ctx->sh_fp);
-    S.zero(S.ctrl, 256 * 4);
+    S.zero(S.ctrl, SC_WORDS * 4);
   } else {
     // ---- 0: global row numbering (rank blocks are consecutive in file
     // order); the first collective carries every rank's status
@@ -1716,14 +1717,15 @@ int classify_sharded_impl(Shard &S, const rk_frags_soa *in, const rk_params *prm
       finish_stats(S, nl, out, t0);
       return r;
     }
-    S.zero(S.ctrl, 256 * 4);
+    S.zero(S.ctrl, SC_WORDS * 4);
   }
   ss.generic_driver = 1;
 
   // ---- 1: processing keys, slice bounds from the global xStart/10 histogram
   Frags f{in->x_start, in->y_start, in->length, in->strand, nl};
   uint32_t *pkey_in = S.take<uint32_t>(SL_PKEY_IN, nl + 1);
-  prep_keys(f, vsize, max_x, max_y, pkey_in, nullptr, S.ctrl + 1, S.ctrl, S.st);
+  prep_keys(f, vsize, max_x, max_y, pkey_in, nullptr, S.ctrl + SC_KEPT, S.ctrl + SC_ERR,
+            S.st);
   S.launched("prep_keys");
   S.agree_errors();
   bool fast32 = true;
@@ -1748,7 +1750,7 @@ int classify_sharded_impl(Shard &S, const rk_frags_soa *in, const rk_params *prm
   if (m) {
     kt_begin(S.st, KID_SH_ROWKEYS);
     k_row_keys<<<grid_for(m, 256, 1024), 256, 0, S.st>>>(
-        rec, m, pkey2, reinterpret_cast<unsigned long long *>(S.ctrl + 10));
+        rec, m, pkey2, reinterpret_cast<unsigned long long *>(S.ctrl + SC_MAXLEN64));
     kt_end(S.st, KID_SH_ROWKEYS, 0.0);
     S.launched("k_row_keys");
     const size_t rw = radix_scratch_words(m);
@@ -1776,13 +1778,13 @@ int classify_sharded_impl(Shard &S, const rk_frags_soa *in, const rk_params *prm
     for (uint32_t g = me + 1; g < P; ++g) thr_min = gop.thr[g] < thr_min ? gop.thr[g] : thr_min;
     uint32_t k0 = m;
     if (thr_min != ~0ull && m) {
-      const std::vector<uint32_t> lw = S.d2h(S.ctrl + 10, 2);
+      const std::vector<uint32_t> lw = S.d2h(S.ctrl + SC_MAXLEN64, 2);
       const uint64_t half = ((uint64_t)lw[0] | ((uint64_t)lw[1] << 32)) / 2;
       const uint64_t reach = thr_min * 100;  // centre >= reach is needed
       const uint64_t key0 = reach > half + 10 ? (reach - half) / 10 - 1 : 0;
-      k_lower_bound<<<1, 1, 0, S.st>>>(pr.pkey, m, key0, S.ctrl + 12);
+      k_lower_bound<<<1, 1, 0, S.st>>>(pr.pkey, m, key0, S.ctrl + SC_LOWER);
       S.launched("k_lower_bound");
-      k0 = S.read1(S.ctrl + 12);
+      k0 = S.read1(S.ctrl + SC_LOWER);
     }
     gop.base = k0;
   }
@@ -1874,7 +1876,7 @@ int classify_sharded_impl(Shard &S, const rk_frags_soa *in, const rk_params *prm
   pr.hrec = S.take<ulonglong2>(SL_HREC, m + 1);
   const uint32_t ybits = (uint32_t)bit_length(2ull * nby - 1);
   const AxisIn ya{yrec_l, ylh_l, keyy_l, par_l, nullptr, ny, ybits, max_y, false, fast32};
-  S.zero(S.ctrl + 6, 4);
+  S.zero(S.ctrl + SC_WIDE_KEYS, 4);
   S.hip(hipEventRecord(ctx->fork, S.st), "fork");
   S.hip(hipStreamWaitEvent(S.st2, ctx->fork, 0), "fork wait");
   if (ny) {
@@ -1888,7 +1890,7 @@ int classify_sharded_impl(Shard &S, const rk_frags_soa *in, const rk_params *prm
   {
     Proc q = pr;
     q.row = grow_proc;  // the member records carry global file rows
-    sort_keys(q, m, S.ctrl + 6, S.st2);  // in-group keys, for the member stage
+    sort_keys(q, m, S.ctrl + SC_WIDE_KEYS, S.st2);  // in-group keys, for the member stage
   }
   S.launched("stream-2 work");
   S.hip(hipEventRecord(ctx->join, S.st2), "join");
@@ -1947,12 +1949,13 @@ int classify_sharded_impl(Shard &S, const rk_frags_soa *in, const rk_params *prm
       ctx->err = "X halo state count mismatch";
       throw RK_E_INTERNAL;
     }
-    S.zero(S.ctrl + 2, 4);
+    S.zero(S.ctrl + SC_MISMATCH, 4);
     if (G) {
-      k_cmp_x<<<grid_for(G, 256, 1024), 256, 0, S.st>>>(gh, G, rel_x, xused, xown, S.ctrl + 2);
+      k_cmp_x<<<grid_for(G, 256, 1024), 256, 0, S.st>>>(gh, G, rel_x, xused, xown,
+                                                           S.ctrl + SC_MISMATCH);
       S.launched("k_cmp_x");
     }
-    const uint32_t mism = S.read1(S.ctrl + 2);
+    const uint32_t mism = S.read1(S.ctrl + SC_MISMATCH);
     if (S.sum_any(mism) == 0) break;
     if (mism) {  // re-resolve with the halo fixed to the owners' states
       ++ss.x_reruns;
@@ -2041,7 +2044,7 @@ int classify_sharded_impl(Shard &S, const rk_frags_soa *in, const rk_params *prm
   // ---- 6: members -> gid-range owners; exact in-group order; emit
   const auto tm = std::chrono::steady_clock::now();
   bool narrow = true;  // the sort keys came from stream 2 (joined before the Y sweeps)
-  for (uint32_t w : S.gather1<uint32_t>(S.read1(S.ctrl + 6))) narrow &= w == 0;
+  for (uint32_t w : S.gather1<uint32_t>(S.read1(S.ctrl + SC_WIDE_KEYS))) narrow &= w == 0;
   MemOp mop{gid_own, pr.hrec, {}, bin_shift(Gtot), nullptr};
   const Bounds gb = split_bounds(global_hist(S, mop, m), mop.shift, Gtot, P);
   mop.B = gb;
@@ -2075,7 +2078,8 @@ int classify_sharded_impl(Shard &S, const rk_frags_soa *in, const rk_params *prm
     build_records(gmem, mem, mr, reckey, tag, S.st);
     // the group-sort tiers on both streams, as in the single-device path
     S.check(sort_groups_exact(sgid, goffs, Gl, mr, reckey, tag, otag, gsort,
-                              S.scan_scratch(SL_SCAN, mr + Gl + 2), ctx->host + 128, narrow, S.st,
+                              S.scan_scratch(SL_SCAN, mr + Gl + 2), ctx->host + HOST_SCRATCH,
+                              narrow, S.st,
                               S.st2 != S.st ? S.st2 : nullptr, ctx->fork, ctx->join));
     emit_result(otag, sgid, goffs, gmem, mr, ogid, orep, oord, S.st);
     if (g0) k_add_u32<<<grid_for(mr, 256), 256, 0, S.st>>>(ogid, mr, g0);

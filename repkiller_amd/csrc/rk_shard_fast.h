@@ -46,18 +46,16 @@
 
 constexpr int RK_SHARD_RETRY = 1 << 21;  // not a status: repeat on the careful driver
 
-// fast-path control words S.ctrl[FW + i]: [0] retry bits, [1] X halo
-// mismatches, [2] Y halo mismatches, [3] X axis left open, [4] Y axis left
-// open, [5] deferred heap segments
-constexpr uint32_t FW = 200;
+// bits of the fast path's retry word (SC_F_RETRY; the fast words: rk_ctrl.h)
 enum : uint32_t { RETRY_EXPECT = 1u, RETRY_PARENT = 2u };
 
 // message layouts (byte offsets into the payload)
 constexpr size_t GA_HOST = 0;     // u64 rows of this rank, u64 fingerprints[8]
-constexpr size_t GA_WORDS = 128;  // u32[32]: [0] error bits, [20] no pack, [21] longest, [25] kept
+constexpr size_t GA_WORDS = 128;  // u32[32]: SC_ERR, SC_NOPACK, SC_MAXLEN, SC_REC_KEPT
 constexpr size_t GA_XH = 256, GA_YH = GA_XH + NBINS * 4, GA_END = GA_YH + NBINS * 4;
 static_assert(GA_END <= GMAX, "GA message");
-constexpr size_t GW_END = 64;  // GC / GD / GE: u32[16] head = ctrl[0..8) + ctrl[FW..FW+8)
+constexpr size_t GW_END = 2 * GW_HALF * 4;  // GC / GD / GE: the head (k_msg_head; gw_head(SC_*))
+static_assert(GW_END == 64, "the message head is fixed");
 static_assert(GW_END + (2 * MAXP + MAXP * MAXP + 2) * 4 <= GMAX, "GC message");
 static_assert(GW_END + 256 + NBINS * 4 <= GMAX, "GD message");
 
@@ -81,22 +79,22 @@ inline uint64_t hbytes(uint64_t h, const void *p, size_t n) {
 }
 
 // ---- kernels ----------------------------------------------------------------
-// the one-route's order-histogram words (k_nw_order_hist: [0] error bits, [1]
-// kept, [3] no pack, [4] longest) in k_sh_rows' layout
+// the one-route's order-histogram words (k_nw_order_hist's, CW_*) in
+// k_sh_rows' layout (SC_*)
 __global__ void k_sh_one_words(const uint32_t *c, uint32_t *w) {
   if (threadIdx.x == 0) {
-    w[0] = c[0];
-    w[20] = c[3];
-    w[21] = c[4];
-    w[25] = c[1];
+    w[SC_ERR] = c[CW_ERR];
+    w[SC_NOPACK] = c[CW_NOPACK];
+    w[SC_MAXLEN] = c[CW_MAXLEN];
+    w[SC_REC_KEPT] = c[CW_KEPT];
   }
 }
 
 // head of the GC / GD / GE messages: the error / flag words and the fast words
 __global__ void k_msg_head(const uint32_t *ctrl, uint32_t *w) {
   const uint32_t t = threadIdx.x;
-  if (t < 8) w[t] = ctrl[t];
-  else if (t < 16) w[t] = ctrl[FW + t - 8];
+  if (t < GW_HALF) w[t] = ctrl[t];
+  else if (t < 2 * GW_HALF) w[t] = ctrl[SC_FAST + t - GW_HALF];
 }
 
 // per source row, with the bounds of every slice, Y range and lead-in: the Y
@@ -345,16 +343,16 @@ int classify_sharded_fast(Shard &S, const Geom &geo, const rk_frags_soa *in, con
     (void)S.status_gather(pre, nullptr, nullptr, 0);
     throw pre;
   }
-  uint32_t *F = S.ctrl + FW;
-  S.expect_flag = F;
+  S.expect_flag = S.ctrl + SC_F_RETRY;
   S.expect_bit = RETRY_EXPECT;
   ss.fast_path = 1;
   const bool solo = P == 1;
   auto tphase = std::chrono::steady_clock::now();
   // the sweeps queued, as many as the last careful call took; an axis left
-  // open sets F[3] (X) / F[4] (Y)
+  // open sets SC_F_OPEN_X / SC_F_OPEN_Y
   const auto resolve = [&](const Axis &a, const SweepScratch &sc, int axis) {
-    S.check(resolve_axis_queued(ctx, a, sc, ctx->sh_blind[axis], F + 3 + axis));
+    S.check(resolve_axis_queued(ctx, a, sc, ctx->sh_blind[axis],
+                                S.ctrl + (axis ? SC_F_OPEN_Y : SC_F_OPEN_X)));
   };
 
   // ---- GA: rows, checks, the slice and Y-range histograms ---------------------
@@ -362,11 +360,11 @@ int classify_sharded_fast(Shard &S, const Geom &geo, const rk_frags_soa *in, con
   const uint32_t nl = R.nl, shift = R.shift, nby = R.nby;
   uint8_t *pay = S.msg_begin(P > 1 ? GA_END : GA_XH);
   uint32_t *wa = reinterpret_cast<uint32_t *>(pay + GA_WORDS);
-  S.zero(F, 16 * 4);
+  S.zero(S.ctrl + SC_FAST, SC_FAST_CLEARED * 4);
   source_rows(S, R, wa, P > 1 ? reinterpret_cast<uint32_t *>(pay + GA_XH) : nullptr,
               P > 1 ? reinterpret_cast<uint32_t *>(pay + GA_YH) : nullptr);
   if (R.one && nl) {
-    k_sh_one_words<<<1, 64, 0, st>>>(S.ctrl + 32, wa);
+    k_sh_one_words<<<1, 64, 0, st>>>(S.ctrl + SC_ONE, wa);
     S.launched("k_sh_one_words");
   }
   {
@@ -389,11 +387,11 @@ int classify_sharded_fast(Shard &S, const Geom &geo, const rk_frags_soa *in, con
     const uint32_t *w = reinterpret_cast<const uint32_t *>(mq + GA_WORDS);
     N += nall[q];
     row_base += q < me ? nall[q] : 0;
-    anyerr |= w[0];
-    nopack |= w[20];
-    R.maxlen = w[21] > R.maxlen ? w[21] : R.maxlen;
-    kept[q] = w[25];
-    fp = hmix(hmix(hmix(fp, nall[q]), kept[q]), w[21]);
+    anyerr |= w[SC_ERR];
+    nopack |= w[SC_NOPACK];
+    R.maxlen = w[SC_MAXLEN] > R.maxlen ? w[SC_MAXLEN] : R.maxlen;
+    kept[q] = w[SC_REC_KEPT];
+    fp = hmix(hmix(hmix(fp, nall[q]), kept[q]), w[SC_MAXLEN]);
     if (P > 1) {
       const uint32_t *hx = reinterpret_cast<const uint32_t *>(mq + GA_XH);
       const uint32_t *hy = reinterpret_cast<const uint32_t *>(mq + GA_YH);
@@ -557,7 +555,7 @@ int classify_sharded_fast(Shard &S, const Geom &geo, const rk_frags_soa *in, con
     // the suffix starts on the device (no readback): entries before it select
     // nothing
     lead_in_suffix(S, R, thr);
-    gop.dbase = S.ctrl + 22;
+    gop.dbase = S.ctrl + SC_LEAD_IN;
     S.plan_counts(gop, m, hpp, hsend);
   } else {
     S.zero_plan(0, hpp);
@@ -606,7 +604,7 @@ int classify_sharded_fast(Shard &S, const Geom &geo, const rk_frags_soa *in, con
     const uint8_t *xown = ex_halo(sop.sout, spp, SL_XOWN, &G2);
     if (G) {
       k_cmp_x16<<<grid_for(G, 256, 1024), 256, 0, st>>>(hx, G, relevant_from(R, me), R.xused, xown,
-                                                        F + 1);
+                                                        S.ctrl + SC_F_MISM_X);
       S.launched("k_cmp_x16");
     }
     ss.x_rounds = 1;
@@ -629,7 +627,7 @@ int classify_sharded_fast(Shard &S, const Geom &geo, const rk_frags_soa *in, con
     // atomics on a few shared words, and 65536 blocks serialised them there)
     k_sh_y_results_fast<<<grid_for(ny, 256, 2048), 256, 0, st>>>(
         R.yr, R.ycode, ny, R.par_l, R.ystate, R.ywin, poff, m, xg, slices, me, gc_pc, gc_rc, gc_lk,
-        F);
+        S.ctrl + SC_F_RETRY);
     kt_end(st, KID_SH_YRES, 0.0);
     S.launched("k_sh_y_results_fast");
   }
@@ -675,7 +673,8 @@ int classify_sharded_fast(Shard &S, const Geom &geo, const rk_frags_soa *in, con
       throw RK_E_INTERNAL;
     }
     if (nrel) {
-      k_cmp_y<<<grid_for(nrel, 256, 1024), 256, 0, st>>>(relidx, nrel, R.yused, rys, F + 2);
+      k_cmp_y<<<grid_for(nrel, 256, 1024), 256, 0, st>>>(relidx, nrel, R.yused, rys,
+                                                         S.ctrl + SC_F_MISM_Y);
       S.launched("k_cmp_y");
     }
     ss.y_rounds = 1;
@@ -694,9 +693,9 @@ int classify_sharded_fast(Shard &S, const Geom &geo, const rk_frags_soa *in, con
   // the careful way)
   const auto roots = [&](const ParRec *prr, uint32_t npar) {
     local_roots(S, rb, xg, prr, npar, m, poff, [&](Proc jp, uint32_t *isnew) {
-      S.zero(S.ctrl + 3, 4);
-      jump_listed(jp, m, isnew, S.ctrl, S.take<uint32_t>(SL_JLIST, m + 1), S.ctrl + 10,
-                  S.ctrl + 3, st);
+      S.zero(S.ctrl + SC_JUMP, 4);
+      jump_listed(jp, m, isnew, S.ctrl, S.take<uint32_t>(SL_JLIST, m + 1), S.ctrl + SC_CHAINS,
+                  S.ctrl + SC_JUMP, st);
       S.launched("jump_listed");
     });
   };
@@ -714,9 +713,11 @@ int classify_sharded_fast(Shard &S, const Geom &geo, const rk_frags_soa *in, con
   std::vector<uint64_t> Pm((size_t)P * P, 0), Rt(P, 0), Lm((size_t)P * P, 0);
   for (uint32_t q = 0; q < P; ++q) {
     const uint32_t *w = reinterpret_cast<const uint32_t *>(S.msg_of(q));
-    anyerr2 |= w[0];
-    wide |= w[6];
-    retry |= w[8] | w[9] | w[10] | w[11] | w[12] | (P == 1 ? w[3] : 0u);
+    anyerr2 |= w[gw_head(SC_ERR)];
+    wide |= w[gw_head(SC_WIDE_KEYS)];
+    retry |= w[gw_head(SC_F_RETRY)] | w[gw_head(SC_F_MISM_X)] | w[gw_head(SC_F_MISM_Y)] |
+             w[gw_head(SC_F_OPEN_X)] | w[gw_head(SC_F_OPEN_Y)] |
+             (P == 1 ? w[gw_head(SC_JUMP)] : 0u);
     const uint32_t *pc = w + GW_END / 4, *rc = pc + P, *lk = rc + P;
     for (uint32_t s = 0; s < P; ++s) {
       Pm[(size_t)q * P + s] = pc[s];
@@ -760,7 +761,8 @@ int classify_sharded_fast(Shard &S, const Geom &geo, const rk_frags_soa *in, con
     const ParRec *prr = xchg<ParRec>(S, knownB, pop.out, ppp, pfrom, SL_PR, &npar);
     roots(prr, npar);
     if (m) {
-      k_expect1<<<1, 64, 0, st>>>(lrank + m, (uint32_t)Rt[me], F, RETRY_EXPECT);
+      k_expect1<<<1, 64, 0, st>>>(lrank + m, (uint32_t)Rt[me], S.ctrl + SC_F_RETRY,
+                                  RETRY_EXPECT);
       S.launched("k_expect1");
     }
     // cross-slice links: request rounds, the first sized by the links the Y
@@ -827,9 +829,9 @@ int classify_sharded_fast(Shard &S, const Geom &geo, const rk_frags_soa *in, con
       std::vector<uint64_t> C((size_t)P * P, 0);
       for (uint32_t q = 0; q < P; ++q) {
         const uint32_t *w = reinterpret_cast<const uint32_t *>(S.msg_of(q));
-        anyerr3 |= w[0];
-        jflag |= w[3];
-        rflag |= w[8];
+        anyerr3 |= w[gw_head(SC_ERR)];
+        jflag |= w[gw_head(SC_JUMP)];
+        rflag |= w[gw_head(SC_F_RETRY)];
         if (links) {
           const uint32_t *t = w + GW_END / 4;
           for (uint32_t d = 0; d < P; ++d) {
@@ -924,8 +926,8 @@ int classify_sharded_fast(Shard &S, const Geom &geo, const rk_frags_soa *in, con
                  : (const void *)ex((const uint4 *)mop.out, mpp, SL_MEM, &mr);
   }
   // (the depth-limit heap segments -- crafted inputs only -- are counted into
-  // F[5] and sorted after GE)
-  member_order(S, R, mem, mr, gb, narrow, erk, gid_own, F + 5);
+  // SC_F_HEAPS and sorted after GE)
+  member_order(S, R, mem, mr, gb, narrow, erk, gid_own, S.ctrl + SC_F_HEAPS);
   S.alloc_locked = false;
 
   // ---- GE: the error bits and the heap segments ---------------------------------
@@ -937,17 +939,17 @@ int classify_sharded_fast(Shard &S, const Geom &geo, const rk_frags_soa *in, con
   bool heap_any = false;
   for (uint32_t q = 0; q < P; ++q) {
     const uint32_t *w = reinterpret_cast<const uint32_t *>(S.msg_of(q));
-    anyerr4 |= w[0];
-    retry4 |= w[8];  // a member plan whose device counts disagreed
-    heap_any |= w[8 + 5] != 0;
-    if (q == me) heap_me = w[8 + 5];
+    anyerr4 |= w[gw_head(SC_ERR)];
+    retry4 |= w[gw_head(SC_F_RETRY)];  // a member plan whose device counts disagreed
+    heap_any |= w[gw_head(SC_F_HEAPS)] != 0;
+    if (q == me) heap_me = w[gw_head(SC_F_HEAPS)];
   }
   if (retry4) return RK_SHARD_RETRY;
   S.check(err_status(ctx, anyerr4 & ~(uint32_t)ERRB_WIDE_LENGTH));
   int hrc = RK_OK;
   if (heap_me && mr) {  // sorted now, then the result again
     hrc = sort_groups_heap_deferred(R.Gl, mr, R.reckey, R.tag, R.otag, R.gsort, heap_me,
-                                    ctx->host + 128, st);
+                                    ctx->host + HOST_SCRATCH, st);
     if (!hrc) {
       emit_members(S, R);
       if (hipGetLastError() != hipSuccess) hrc = RK_E_HIP;

@@ -68,8 +68,8 @@ __device__ __forceinline__ uint32_t nwy_bucket(const uint3 &r, uint32_t nby) {
 }
 
 // ---- source side: processing keys, the checks, the slice histogram --------
-// ctrl: [0] error bits, [20] some kept row does not pack, [21] longest kept
-// length, [25] kept rows
+// ctrl: SC_ERR, SC_NOPACK, SC_MAXLEN, SC_REC_KEPT (the sharded block, or the
+// fast path's GA message words)
 struct ShRowsArgs {
   Frags f;
   uint64_t vsize, max_x, max_y;
@@ -127,11 +127,11 @@ __global__ void __launch_bounds__(256) k_sh_rows(ShRowsArgs a) {
     for (uint32_t b = threadIdx.x; b < NBINS; b += 256)
       if (hy[b]) atomicAdd(&a.yhist[b], hy[b]);
   if (threadIdx.x == 0) {
-    if (red[2]) atomicAdd(&a.ctrl[25], red[2]);
-    if (red[0]) atomicMax(&a.ctrl[21], red[0]);
-    if (red[1] & 1u) atomicOr(&a.ctrl[0], ERRB_UB_BUCKET);
-    if (red[1] & 2u) atomicOr(&a.ctrl[0], ERRB_UB_CENTER);
-    if (red[1] & 4u) atomicOr(&a.ctrl[20], 1u);
+    if (red[2]) atomicAdd(&a.ctrl[SC_REC_KEPT], red[2]);
+    if (red[0]) atomicMax(&a.ctrl[SC_MAXLEN], red[0]);
+    if (red[1] & 1u) atomicOr(&a.ctrl[SC_ERR], ERRB_UB_BUCKET);
+    if (red[1] & 2u) atomicOr(&a.ctrl[SC_ERR], ERRB_UB_CENTER);
+    if (red[1] & 4u) atomicOr(&a.ctrl[SC_NOPACK], 1u);
   }
 }
 
@@ -428,17 +428,17 @@ static uint64_t slice_max_rows(const std::vector<uint64_t> &gh, const Bounds &sk
 // Source rows: keys, checks and histograms.  World size 1 (R.one, rows
 // numbered from 0): the rows are read once, as on one device --
 // k_nw_order_hist takes the checks, the kept count and the order and Y digit
-// histograms (into ahist / yhist) in the place of k_sh_rows, its words in
-// ctrl[32..) ([0] error bits, [1] kept, [3] no pack, [4] longest).  Else
+// histograms (into ahist / yhist) in the place of k_sh_rows, its words (CW_*)
+// from SC_ONE on.  Else
 // k_sh_rows: its words into `words` (ShRowsArgs' layout), the xStart/10 and
 // Y-centre bucket histograms into xhist / yhist (null: not needed).
 void source_rows(Shard &S, const RecState &R, uint32_t *words, uint32_t *xhist, uint32_t *yhist) {
   if (R.one) {
     S.zero(R.ahist, 3 * 4096 * 4);
-    S.zero(S.ctrl + 32, 16 * 4);
+    S.zero(S.ctrl + SC_ONE, SC_ONE_WORDS * 4);
     if (R.nl)
       nw_order_hist(*R.in, R.vsize, R.max_x, R.max_y, R.nby, R.op1.nseg ? R.op1.coarse : R.ad,
-                    R.yd, R.ahist, R.yhist, S.ctrl + 32, S.st);
+                    R.yd, R.ahist, R.yhist, S.ctrl + SC_ONE, S.st);
   } else if (R.nl) {
     ShRowsArgs ra{R.f, R.vsize, R.max_x, R.max_y, R.shift, xhist, words};
     if (yhist) ra.yhist = yhist, ra.yshift = R.yshift;
@@ -644,7 +644,7 @@ void y_beside_x(Shard &S, const RecState &R, bool codes) {
 
 // ---- X lead-in halo
 // The start of the slice's suffix whose centres can reach a later slice's
-// lead-in, into ctrl[22] (false: no later slice has one, or the slice is empty)
+// lead-in, into SC_LEAD_IN (false: no later slice has one, or the slice is empty)
 bool lead_in_suffix(Shard &S, const RecState &R, const uint64_t *thr) {
   uint64_t thr_min = ~0ull;
   for (uint32_t g = S.me + 1; g < S.P; ++g) thr_min = thr[g] < thr_min ? thr[g] : thr_min;
@@ -652,7 +652,7 @@ bool lead_in_suffix(Shard &S, const RecState &R, const uint64_t *thr) {
   const uint64_t reach = thr_min * 100;  // centre >= reach is needed
   const uint64_t half = R.maxlen / 2;
   const uint64_t key0 = reach > half + 10 ? (reach - half) / 10 - 1 : 0;
-  k_lower_bound16<<<1, 1, 0, S.st>>>(R.Ra, R.m, key0, S.ctrl + 22);
+  k_lower_bound16<<<1, 1, 0, S.st>>>(R.Ra, R.m, key0, S.ctrl + SC_LEAD_IN);
   S.launched("k_lower_bound16");
   return true;
 }
@@ -666,7 +666,7 @@ uint64_t relevant_from(const RecState &R, uint32_t me) {
 void x_buffers(Shard &S, RecState &R, uint32_t G) {
   R.xg = S.take<uint32_t>(SL_XG, R.m + 1);
   R.xused = S.take<uint8_t>(SN_XGUSED, G + 1);
-  S.zero(S.ctrl + 6, 4);
+  S.zero(S.ctrl + SC_WIDE_KEYS, 4);
 }
 // resolve(axis, scratch, 0): the sweeps, with readbacks (resolve_axis) or
 // queued (resolve_axis_queued); own(xpos, state, par, mx): the own results
@@ -711,7 +711,7 @@ void solve_x(Shard &S, RecState &R, const uint4 *halo, uint32_t Gc, uint32_t *pa
           R.p.len_ratio, R.p.pos_ratio};
   SweepScratch sc{S.take<uint32_t>(SL_RUNS, runs_scratch_words(mx)),
                   S.take<uint8_t>(SL_WPEND, mx / 64 + 1), S.take<uint8_t>(SL_RPEND, mx),
-                  S.ctrl + 64, S.ctrl + 4};
+                  S.ctrl + SC_PEND, S.ctrl + SC_SWEEP_COUNT};
   resolve(ax, sc, 0);
   own(xpos, cx.state, par, mx);
 }
@@ -760,7 +760,7 @@ void sweep_y(Shard &S, const RecState &R, uint32_t n, uint32_t *par, Resolve &&r
   ay.par_dev = true;
   SweepScratch sc{S.take<uint32_t>(SL_RUNS, runs_scratch_words(n)),
                   S.take<uint8_t>(SL_WPEND, n / 64 + 1), S.take<uint8_t>(SL_RPEND, n),
-                  S.ctrl + 64, S.ctrl + 4};
+                  S.ctrl + SC_PEND, S.ctrl + SC_SWEEP_COUNT};
   resolve(ay, sc, 1);
 }
 
@@ -818,8 +818,9 @@ void member_order(Shard &S, RecState &R, const void *mem, uint32_t mr, const Bou
   group_offsets(R.sgid, mr, Gl, R.goffs, st);
   // the group-sort tiers on both streams, as in the single-device path
   const int rc = sort_groups_exact(R.sgid, R.goffs, Gl, mr, R.reckey, R.tag, R.otag, R.gsort,
-                                   S.scan_scratch(SL_SCAN, mr + Gl + 2), ctx->host + 128, narrow,
-                                   st, st2 != st ? st2 : nullptr, ctx->fork, ctx->join, heap_count);
+                                   S.scan_scratch(SL_SCAN, mr + Gl + 2), ctx->host + HOST_SCRATCH,
+                                   narrow, st, st2 != st ? st2 : nullptr, ctx->fork, ctx->join,
+                                   heap_count);
   if (!heap_count) S.check(rc);
   emit_members(S, R);
   S.launched("member order");
@@ -849,28 +850,29 @@ int classify_sharded_nw(Shard &S, const Geom &geo, const rk_frags_soa *in, const
   // ---- 1: keys, checks and the slice histogram at the source; every rank
   // agrees on the record layout (or all run the generic driver)
   S.zero(R.ahist, NBINS * 4);  // (the slice histogram; later the sorts' digit histograms)
-  S.zero(S.ctrl + 25, 4);
+  S.zero(S.ctrl + SC_REC_KEPT, 4);
   source_rows(S, R, S.ctrl, P > 1 ? R.ahist : nullptr, nullptr);
-  // the error bits (ctrl[0]), the pack flags (ctrl[20..21]), the kept count
-  // (ctrl[25]) and the slice histogram in one readback, and the first two with
-  // the histogram in one all-gather
-  std::vector<uint32_t> flags(41);
+  // the error bits, the pack flag and the longest length, the kept count and
+  // the slice histogram in one readback, and the first three with the
+  // histogram in one all-gather
+  std::vector<uint32_t> flags(RB_SH_ROWS_ONE_N);
   const uint32_t MW = 2 + (P > 1 ? NBINS : 0);  // message words
   std::vector<uint32_t> msg(MW);
-  S.hip(hipMemcpyAsync(flags.data(), S.ctrl, (R.one ? 41 : 26) * 4, hipMemcpyDeviceToHost, st),
+  S.hip(hipMemcpyAsync(flags.data(), S.ctrl + SC_ERR,
+                       (R.one ? RB_SH_ROWS_ONE_N : RB_SH_ROWS_N) * 4, hipMemcpyDeviceToHost, st),
         "d2h");
   if (P > 1)
     S.hip(hipMemcpyAsync(msg.data() + 2, R.ahist, NBINS * 4, hipMemcpyDeviceToHost, st), "d2h");
   ++S.n_syncs;
   S.hip(hipStreamSynchronize(st), "d2h sync");
   if (R.one) {  // k_nw_order_hist's words in k_sh_rows' layout
-    flags[0] = flags[32];
-    flags[25] = flags[33];
-    flags[20] = flags[35];
-    flags[21] = flags[36];
+    flags[SC_ERR] = flags[SC_ONE + CW_ERR];
+    flags[SC_REC_KEPT] = flags[SC_ONE + CW_KEPT];
+    flags[SC_NOPACK] = flags[SC_ONE + CW_NOPACK];
+    flags[SC_MAXLEN] = flags[SC_ONE + CW_MAXLEN];
   }
-  msg[0] = flags[0];
-  msg[1] = flags[20] | (flags[21] << 1);
+  msg[0] = flags[SC_ERR];
+  msg[1] = flags[SC_NOPACK] | (flags[SC_MAXLEN] << 1);
   std::vector<uint32_t> allm((size_t)P * MW);
   S.allgather(msg.data(), allm.data(), MW * 4);
   uint32_t anyerr = 0, nopack = 0;
@@ -885,7 +887,7 @@ int classify_sharded_nw(Shard &S, const Geom &geo, const rk_frags_soa *in, const
   }
   S.check(err_status(ctx, anyerr & ~(uint32_t)ERRB_WIDE_LENGTH));
   if (nopack) return RK_SHARD_FALLBACK;
-  R.kept = flags[25];
+  R.kept = flags[SC_REC_KEPT];
   R.slice_keys = split_bounds(gh, R.shift, R.drop, P);
   // the one-sweep passes' status words carry a 30-bit count (SW_VAL,
   // rk_onesweep.h), as the single-device record pipeline's bound n < 2^30
@@ -930,7 +932,7 @@ int classify_sharded_nw(Shard &S, const Geom &geo, const rk_frags_soa *in, const
   gop.me = me;
   gop.poff = R.poff;
   lead_in_thresholds(gop.thr, R.mall, R.slice_keys, R.H);
-  gop.base = lead_in_suffix(S, R, gop.thr) ? S.read1(S.ctrl + 22) : m;
+  gop.base = lead_in_suffix(S, R, gop.thr) ? S.read1(S.ctrl + SC_LEAD_IN) : m;
   const uint32_t nsuf = m - gop.base;
   PartPlan pp;
   if (nsuf) S.plan(gop, nsuf, pp);
@@ -976,12 +978,13 @@ int classify_sharded_nw(Shard &S, const Geom &geo, const rk_frags_soa *in, const
       ctx->err = "X halo state count mismatch";
       throw RK_E_INTERNAL;
     }
-    S.zero(S.ctrl + 2, 4);
+    S.zero(S.ctrl + SC_MISMATCH, 4);
     if (G) {
-      k_cmp_x16<<<grid_for(G, 256, 1024), 256, 0, st>>>(hx, G, rel_x, R.xused, xown, S.ctrl + 2);
+      k_cmp_x16<<<grid_for(G, 256, 1024), 256, 0, st>>>(hx, G, rel_x, R.xused, xown,
+                                                        S.ctrl + SC_MISMATCH);
       S.launched("k_cmp_x16");
     }
-    const uint32_t mism = S.read1(S.ctrl + 2);
+    const uint32_t mism = S.read1(S.ctrl + SC_MISMATCH);
     if (S.sum_any(mism) == 0) break;
     if (mism) {  // re-resolve with the halo fixed to the owners' states
       ++ss.x_reruns;
@@ -1058,8 +1061,8 @@ int classify_sharded_nw(Shard &S, const Geom &geo, const rk_frags_soa *in, const
   // readback and one all-gather
   std::vector<uint32_t> wide;
   std::vector<uint64_t> ghist(NBINS, 0);
-  if (P > 1) ghist = global_hist(S, mop, m, {S.ctrl + 6}, &wide);
-  else wide = S.gather1<uint32_t>(S.read1(S.ctrl + 6));
+  if (P > 1) ghist = global_hist(S, mop, m, {S.ctrl + SC_WIDE_KEYS}, &wide);
+  else wide = S.gather1<uint32_t>(S.read1(S.ctrl + SC_WIDE_KEYS));
   bool narrow = true;  // every sort key fits 32 bits
   for (uint32_t w : wide) narrow &= w == 0;
   mop.narrow = narrow;
