@@ -456,6 +456,65 @@ typedef struct {
 } rk_egress_stats;
 int rk_get_egress_stats(const rk_ctx *ctx, rk_egress_stats *st);
 
+/* ---- batched sets as files: many CSVs parsed and formatted on the GPU ----
+ *
+ * An rk_dbset is one FragmentsDatabase per listed file
+ * (FragmentsDatabase.cpp:17-101, applied per file), held as ONE combined
+ * database: the bodies of all files go to the device as one byte stream (a
+ * body without a final newline gets one, so no line joins the next file's
+ * first), are parsed there as rk_db_load_csv_device parses one body, and set
+ * k's rows are rows [set_off[k], set_off[k + 1]) of the combined columns, in
+ * file order -- the rows, header text and header numbers rk_db_load_csv
+ * produces for paths[k].  The same path may be listed more than once.
+ * flags: 0, RK_DB_KEEP_DEVICE or RK_DB_KEEP_ROWS, as rk_db_load_csv_device.
+ * Errors, in this order: RK_E_ARG (null arguments, a bad flag); RK_E_IO for
+ * the lowest-numbered file that cannot be opened or mapped, before any device
+ * work; after the parse RK_E_COUNT for the lowest-numbered set with more
+ * accepted rows than its own header total (FragmentsDatabase.cpp:99);
+ * RK_E_TOO_MANY when the combined rows reach 2^32 - 1.  rk_last_error names
+ * the set ("set K").  nsets == 0 is RK_OK with an empty set. */
+typedef struct rk_dbset rk_dbset;
+int rk_dbset_load_csv_device(rk_ctx *ctx, const char *const *paths, uint32_t nsets,
+                             uint32_t flags, rk_dbset **out);
+void rk_dbset_free(rk_dbset *dbs);
+/* Borrowed until rk_dbset_free, every out pointer nullable: set_off (nsets + 1
+ * entries), the three header values per set (FragmentsDatabase.cpp:62-69), the
+ * combined HOST SoA and the combined DEVICE SoA (asking for `dev` is RK_E_ARG
+ * unless the set was loaded with RK_DB_KEEP_DEVICE). */
+int rk_dbset_view(const rk_dbset *dbs, uint32_t *nsets, const uint64_t **set_off,
+                  const uint64_t **len_x_hdr, const uint64_t **len_y_hdr,
+                  const uint64_t **total_hdr, rk_frags_soa *host, rk_frags_soa *dev);
+/* rk_classify_device_batch on the resident columns (the work of
+ * repkiller.cpp:80-97 for every set), the result downloaded into the caller's
+ * HOST rk_batch_result (set_off[nsets] entries per array).  Errors as
+ * rk_classify_device_batch returns them. */
+int rk_classify_dbset(rk_ctx *ctx, const rk_dbset *dbs, double len_ratio, double pos_ratio,
+                      rk_batch_result *out);
+/* The host save of ONE set: rk_db_write_csv (commonFunctions.cpp:101-146) for
+ * set k from the combined host columns, under the set's own header; res is
+ * that set's result (out_order local to the set), host arrays. */
+int rk_dbset_write_csv(const rk_dbset *dbs, uint32_t k, const char *path, const rk_result *res);
+/* save_all_frag_pairs (commonFunctions.cpp:101-146) for every set, formatted
+ * on the device from the nine resident columns (RK_DB_KEEP_ROWS): file k is set
+ * k's header followed by the rows rk_db_write_csv writes for set k's result,
+ * byte for byte.  res is in rk_batch_result layout: host arrays, or device
+ * arrays with RK_RES_DEVICE; n_out is always a host array (n_groups is not
+ * read).  A path that cannot be opened is RK_E_IO naming the set: files of
+ * lower-numbered sets are complete, nothing is promised from that set on.  An
+ * out_order entry >= its set's row count is RK_E_ARG.  At most a constant
+ * number of output files is open at any time. */
+int rk_dbset_write_csv_device(rk_ctx *ctx, const rk_dbset *dbs, const char *const *paths,
+                              const rk_batch_result *res, uint32_t flags);
+/* rk_classify_dbset followed by that save (repkiller.cpp:80-97 and
+ * commonFunctions.cpp:101-146 per set), the result arrays never leaving the
+ * device.  n_out / n_groups: nullable HOST arrays, nsets entries.  When the
+ * classification fails no output file is opened or created. */
+int rk_classify_dbset_to_csv(rk_ctx *ctx, const rk_dbset *dbs, double len_ratio, double pos_ratio,
+                             const char *const *paths, uint64_t *n_out, uint64_t *n_groups);
+/* rk_get_ingress_stats / rk_get_egress_stats report the last batched load or
+ * save in their existing fields, the totals running over all sets;
+ * rk_get_batch_stats reports the classification. */
+
 /* ---- synthetic inputs --------------------------------- */
 
 typedef struct {

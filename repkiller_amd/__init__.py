@@ -20,6 +20,8 @@ reference                              here
                                        (on the GPU: ``save_all_frag_pairs_device``,
                                        ``rk_db_write_csv_device``)
 ``SaverQueue``                         :class:`SaverQueue` (``rk_saver_*``)
+one ``FragmentsDatabase`` per file of  :class:`FragmentsDatabaseSet` (``rk_dbset_*``: parsed,
+an all-against-all run                 classified and saved on the GPU as one batch)
 =====================================  ============================================
 """
 from __future__ import annotations
@@ -58,6 +60,8 @@ EXPORTS = (
     "rk_classify_batch", "rk_classify_device_batch", "rk_batch_layout", "rk_get_batch_stats",
     "rk_db_load_csv_device", "rk_db_device_view", "rk_classify_db_pairs", "rk_get_ingress_stats",
     "rk_db_write_csv_device", "rk_classify_db_pairs_to_csv", "rk_get_egress_stats",
+    "rk_dbset_load_csv_device", "rk_dbset_free", "rk_dbset_view", "rk_classify_dbset",
+    "rk_dbset_write_csv_device", "rk_classify_dbset_to_csv", "rk_dbset_write_csv",
 )
 # declared too, returning uint32_t (sizes the device CSV parser was built with)
 EXPORTS_U32 = ("rk_csv_max_line", "rk_csv_tile")
@@ -279,6 +283,23 @@ def load_library() -> ctypes.CDLL:
                                                        ctypes.POINTER(ctypes.c_char_p), _u64p,
                                                        _u64p]),
         "rk_get_egress_stats": (ctypes.c_int, [vp, ctypes.POINTER(EgressStats)]),
+        "rk_dbset_load_csv_device": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_char_p),
+                                                    ctypes.c_uint32, ctypes.c_uint32,
+                                                    ctypes.POINTER(vp)]),
+        "rk_dbset_free": (None, [vp]),
+        "rk_dbset_view": (ctypes.c_int, [vp, _u32p, ctypes.POINTER(_u64p), ctypes.POINTER(_u64p),
+                                         ctypes.POINTER(_u64p), ctypes.POINTER(_u64p),
+                                         ctypes.POINTER(FragsSoA), ctypes.POINTER(FragsSoA)]),
+        "rk_classify_dbset": (ctypes.c_int, [vp, vp, ctypes.c_double, ctypes.c_double,
+                                             ctypes.POINTER(BatchResult)]),
+        "rk_dbset_write_csv": (ctypes.c_int, [vp, ctypes.c_uint32, ctypes.c_char_p,
+                                              ctypes.POINTER(Result)]),
+        "rk_dbset_write_csv_device": (ctypes.c_int, [vp, vp, ctypes.POINTER(ctypes.c_char_p),
+                                                     ctypes.POINTER(BatchResult),
+                                                     ctypes.c_uint32]),
+        "rk_classify_dbset_to_csv": (ctypes.c_int, [vp, vp, ctypes.c_double, ctypes.c_double,
+                                                    ctypes.POINTER(ctypes.c_char_p), _u64p,
+                                                    _u64p]),
         "rk_csv_max_line": (ctypes.c_uint32, []),
         "rk_csv_tile": (ctypes.c_uint32, []),
     }
@@ -470,6 +491,124 @@ class FragmentsDatabase:
             pass
 
 
+class FragmentsDatabaseSet:
+    """One FragmentsDatabase per listed CSV, parsed on the GPU as one combined
+    database (rk_dbset_load_csv_device): set k's rows are rows
+    [set_off[k], set_off[k + 1]) of the combined columns, in file order."""
+
+    def __init__(self, paths, ctx: "Context", keep_device: bool = False,
+                 keep_rows: bool = False):
+        """keep_device=True keeps the four classification columns in HBM
+        (Context.classify_dbset); keep_rows=True keeps all nine
+        (save_all_device, Context.classify_dbset_to_csv)."""
+        lib = load_library()
+        self.paths = [str(p) for p in paths]
+        ns = len(self.paths)
+        arr = (ctypes.c_char_p * max(ns, 1))(*[p.encode() for p in self.paths])
+        h = ctypes.c_void_p()
+        rc = lib.rk_dbset_load_csv_device(ctx._h, arr, ns,
+                                          RK_DB_KEEP_ROWS if keep_rows else
+                                          RK_DB_KEEP_DEVICE if keep_device else 0,
+                                          ctypes.byref(h))
+        if rc != RK_OK:
+            raise RkError(rc, ctx.last_error())
+        self._h = h
+        n = ctypes.c_uint32()
+        off, lx, ly, tot = _u64p(), _u64p(), _u64p(), _u64p()
+        soa = FragsSoA()
+        _check(lib.rk_dbset_view(h, ctypes.byref(n), ctypes.byref(off), ctypes.byref(lx),
+                                 ctypes.byref(ly), ctypes.byref(tot), ctypes.byref(soa), None))
+        self.nsets = int(n.value)
+
+        def arr64(p, count):
+            if count == 0:
+                return np.empty(0, np.uint64)
+            return np.ctypeslib.as_array(p, shape=(count,)).copy()
+
+        self.set_off = arr64(off, self.nsets + 1)
+        self.len_x_hdr = arr64(lx, self.nsets)
+        self.len_y_hdr = arr64(ly, self.nsets)
+        self.total_hdr = arr64(tot, self.nsets)
+        rows = int(soa.n)
+
+        def view(ptr, dtype, count):
+            if count == 0:
+                return np.empty(0, dtype)
+            buf = (ctypes.c_uint8 * (count * np.dtype(dtype).itemsize)).from_address(ptr)
+            return np.frombuffer(buf, dtype=dtype)
+
+        # the combined host columns, borrowed from the library until close()
+        # (not copied: a batch's columns are gigabytes)
+        self._host = Frags(view(soa.x_start, np.uint64, rows), view(soa.y_start, np.uint64, rows),
+                           view(soa.length, np.uint64, rows), view(soa.strand, np.uint8, rows))
+
+    @property
+    def n(self) -> int:
+        """Rows of the combined database (= set_off[nsets])."""
+        return self._host.n
+
+    def frags(self, k: int) -> Frags:
+        """Host rows of set k (what FragmentsDatabase(paths[k]).frags holds), copied."""
+        a, b = int(self.set_off[k]), int(self.set_off[k + 1])
+        h = self._host
+        return Frags(h.x_start[a:b].copy(), h.y_start[a:b].copy(), h.length[a:b].copy(),
+                     h.strand[a:b].copy())
+
+    def device_view(self) -> dict:
+        """The resident combined columns of a set loaded with keep_device=True:
+        device addresses of x_start, y_start, length, strand and the row count."""
+        soa = FragsSoA()
+        _check(load_library().rk_dbset_view(self._h, None, None, None, None, None, None,
+                                            ctypes.byref(soa)),
+               "the set was not loaded with keep_device=True")
+        return {"x_start": soa.x_start or 0, "y_start": soa.y_start or 0,
+                "length": soa.length or 0, "strand": soa.strand or 0, "n": int(soa.n)}
+
+    def save_set(self, k: int, path: str, res: ClassifyResult) -> None:
+        """The host save of set k (rk_dbset_write_csv): save_all_frag_pairs from
+        the combined host columns under the set's own header."""
+        r = res.as_struct()
+        rc = load_library().rk_dbset_write_csv(self._h, k, str(path).encode(), ctypes.byref(r))
+        if rc == -2:
+            raise RkError(rc, "Could not open output directory " + str(path))
+        _check(rc)
+
+    def save_all_device(self, ctx: "Context", paths, results) -> None:
+        """save_all_frag_pairs for every set, formatted on the GPU
+        (rk_dbset_write_csv_device): results[k] is set k's ClassifyResult and goes
+        to paths[k].  Needs keep_rows=True."""
+        paths, results = [str(p) for p in paths], list(results)
+        if len(paths) != self.nsets or len(results) != self.nsets:
+            raise ValueError("save_all_device: one path and one result per set")
+        n = self.n
+        order, gid, rep = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uint8)
+        n_out = np.zeros(max(self.nsets, 1), np.uint64)
+        for k, r in enumerate(results):
+            a, m = int(self.set_off[k]), int(r.out_order.shape[0])
+            if a + m > int(self.set_off[k + 1]):
+                raise ValueError(f"save_all_device: set {k}'s result has more rows than the set")
+            order[a:a + m], gid[a:a + m], rep[a:a + m] = r.out_order, r.gid, r.repval
+            n_out[k] = m
+        res = BatchResult(_ptr(order), _ptr(gid), _ptr(rep), n_out.ctypes.data, 0)
+        arr = (ctypes.c_char_p * max(self.nsets, 1))(*[p.encode() for p in paths])
+        rc = load_library().rk_dbset_write_csv_device(ctx._h, self._h, arr, ctypes.byref(res), 0)
+        if rc != RK_OK:
+            raise RkError(rc, ctx.last_error())
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._host = Frags(np.empty(0, np.uint64), np.empty(0, np.uint64),
+                               np.empty(0, np.uint64), np.empty(0, np.uint8))
+            load_library().rk_dbset_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class SaverQueue:
     """SaverQueue.h:37-41 -- background CSV writer (start / addRequest / stop)."""
 
@@ -632,6 +771,46 @@ class Context:
         if rc != RK_OK:
             raise RkError(rc, self.last_error())
         return [(int(n_out[i]), int(n_groups[i])) for i in range(q)]
+
+    def classify_dbset(self, dbs: "FragmentsDatabaseSet", len_ratio: float = 0.3,
+                       pos_ratio: float = 0.3) -> list:
+        """Classify every set of a keep_device=True FragmentsDatabaseSet from its
+        resident columns in one batched call (rk_classify_dbset); one
+        ClassifyResult per set, as classify_batch returns them."""
+        n, ns = dbs.n, dbs.nsets
+        gid, rep, order = np.zeros(n, np.uint32), np.zeros(n, np.uint8), np.zeros(n, np.uint32)
+        n_out, n_groups = np.zeros(max(ns, 1), np.uint64), np.zeros(max(ns, 1), np.uint64)
+        res = BatchResult(_ptr(order), _ptr(gid), _ptr(rep), n_out.ctypes.data,
+                          n_groups.ctypes.data)
+        rc = load_library().rk_classify_dbset(self._h, dbs._h, len_ratio, pos_ratio,
+                                              ctypes.byref(res))
+        if rc != RK_OK:
+            raise RkError(rc, self.last_error())
+        out = []
+        for k in range(ns):
+            a = int(dbs.set_off[k])
+            b = a + int(n_out[k])
+            out.append(ClassifyResult(gid[a:b].copy(), rep[a:b].copy(), order[a:b].copy(),
+                                      int(n_groups[k])))
+        return out
+
+    def classify_dbset_to_csv(self, dbs: "FragmentsDatabaseSet", paths, len_ratio: float = 0.3,
+                              pos_ratio: float = 0.3) -> tuple:
+        """Classify a keep_rows=True FragmentsDatabaseSet and write set k to
+        paths[k] from the device (rk_classify_dbset_to_csv): the result arrays
+        never come to the host.  Returns (n_out, n_groups) as uint64 arrays."""
+        paths = [str(p) for p in paths]
+        ns = dbs.nsets
+        if len(paths) != ns:
+            raise ValueError("classify_dbset_to_csv: one path per set")
+        arr = (ctypes.c_char_p * max(ns, 1))(*[p.encode() for p in paths])
+        n_out, n_groups = np.zeros(max(ns, 1), np.uint64), np.zeros(max(ns, 1), np.uint64)
+        rc = load_library().rk_classify_dbset_to_csv(
+            self._h, dbs._h, len_ratio, pos_ratio, arr, n_out.ctypes.data_as(_u64p),
+            n_groups.ctypes.data_as(_u64p))
+        if rc != RK_OK:
+            raise RkError(rc, self.last_error())
+        return n_out[:ns], n_groups[:ns]
 
     def egress_stats(self) -> dict:
         """The last device CSV save on this context (rk_get_egress_stats)."""

@@ -22,7 +22,7 @@
 // cache: no parse at all), --device-parse (the CSV body is
 // parsed on the GPU, rk_db_load_csv_device, and every pair is classified from
 // the columns that stay resident there: no second upload; --timing then adds
-// the ingress legs; not with --soa, --batch or --gpus above 1), --device-save
+// the ingress legs; not with --soa or --gpus above 1; with --batch see below), --device-save
 // (only with --device-parse: all nine columns stay resident, RK_DB_KEEP_ROWS,
 // and every pair's output is formatted on the GPU and written from its staging
 // slots, rk_classify_db_pairs_to_csv: the result arrays never reach the host;
@@ -34,6 +34,15 @@
 // <list> holds one "input.csv<TAB>output.csv" per line: the inputs are loaded
 // (at most 16 threads), classified together by ONE rk_classify_batch call and
 // each output written as a run of its own would write it.
+//
+//   rk_repkiller --batch <list> --device-parse [--device-save] [--timing] <len_ratio> <pos_ratio>
+//
+// The listed CSVs are parsed on the GPU as one byte stream into one combined
+// resident database (rk_dbset_load_csv_device) and classified from there
+// (rk_classify_dbset, then the host save per file); with --device-save the
+// outputs are formatted on the GPU too and every set's text goes to its own
+// file (rk_classify_dbset_to_csv).  --timing prints the ingress, batch and
+// egress stats as one JSON line on stderr.
 #include <atomic>
 #include <chrono>
 #include <fstream>
@@ -53,7 +62,7 @@ static void print_help() {
               "[--timing] [--save-soa cache.soa | --soa | --device-parse [--device-save]] <input_file_path> <output_file_path> "
               "<length_ratio> <position_ratio> [<length_ratio> <position_ratio>]...\n");
   std::printf("       ./rk_repkiller [--device N] --batch <list of input<TAB>output lines> "
-              "<length_ratio> <position_ratio>\n");
+              "[--device-parse [--device-save] [--timing]] <length_ratio> <position_ratio>\n");
   std::fflush(stdout);
 }
 
@@ -128,25 +137,120 @@ static int classify_sharded_threads(const rk_frags_soa &soa, int device, int gpu
   return 0;
 }
 
-// --batch: every listed CSV through one batched classification
-static int run_batch(const char *list_path, double lr, double pr, int device) {
+static bool read_batch_list(const char *list_path, std::vector<std::string> &ins,
+                            std::vector<std::string> &outs) {
   std::ifstream lf(list_path);
   if (!lf) {
     std::fprintf(stderr, "Could not open batch list %s.\n", list_path);
-    return 1;
+    return false;
   }
-  std::vector<std::string> ins, outs;
   for (std::string line; std::getline(lf, line);) {
     if (!line.empty() && line.back() == '\r') line.pop_back();
     if (line.empty()) continue;
     const size_t tab = line.find('\t');
     if (tab == std::string::npos || tab == 0 || tab + 1 == line.size()) {
       std::fprintf(stderr, "Batch list line without input<TAB>output: %s\n", line.c_str());
-      return 1;
+      return false;
     }
     ins.push_back(line.substr(0, tab));
     outs.push_back(line.substr(tab + 1));
   }
+  return true;
+}
+
+// --batch --device-parse [--device-save]: the listed CSVs parsed on the GPU into
+// one combined resident database, classified from there; the outputs written by
+// the host per file, or formatted on the GPU too
+static int run_batch_device(const char *list_path, double lr, double pr, int device,
+                            bool device_save, bool timing) {
+  std::vector<std::string> ins, outs;
+  if (!read_batch_list(list_path, ins, outs)) return 1;
+  const size_t ns = ins.size();
+  std::printf("--- Running REPKILLER (MI355X), %zu fragment sets ---\n\n", ns);
+  std::fflush(stdout);
+  rk_ctx *ctx = nullptr;
+  int rc = rk_create(&ctx, device);
+  if (rc) {
+    std::fprintf(stderr, "no usable gfx950 device %d (%d)\n", device, rc);
+    return 1;
+  }
+  std::vector<const char *> ip(ns), op(ns);
+  for (size_t k = 0; k < ns; ++k) ip[k] = ins[k].c_str(), op[k] = outs[k].c_str();
+  rk_dbset *dbs = nullptr;
+  const double t0 = now_s();
+  rc = rk_dbset_load_csv_device(ctx, ip.data(), (uint32_t)ns,
+                                device_save ? (uint32_t)RK_DB_KEEP_ROWS
+                                            : (uint32_t)RK_DB_KEEP_DEVICE,
+                                &dbs);
+  const double t1 = now_s();
+  auto fail = [&](const char *what) {
+    std::fprintf(stderr, "%s failed (%d): %s\n", what, rc, rk_last_error(ctx));
+    rk_dbset_free(dbs);
+    rk_destroy(ctx);
+    return 1;
+  };
+  if (rc == RK_E_COUNT) std::fprintf(stderr, "Unexpected number of fragments\n");
+  if (rc) return fail("device parse");
+  uint32_t nsets = 0;
+  const uint64_t *off = nullptr;
+  rk_dbset_view(dbs, &nsets, &off, nullptr, nullptr, nullptr, nullptr, nullptr);
+  const uint64_t n = off[nsets];
+  std::vector<uint64_t> n_out(ns + 1), n_groups(ns + 1);
+  double t2;
+  if (device_save) {
+    rc = rk_classify_dbset_to_csv(ctx, dbs, lr, pr, op.data(), n_out.data(), n_groups.data());
+    t2 = now_s();
+    if (rc) return fail("classification or device save");
+  } else {
+    std::vector<uint32_t> gid(n), order(n);
+    std::vector<uint8_t> rep(n);
+    rk_batch_result br{order.data(), gid.data(), rep.data(), n_out.data(), n_groups.data()};
+    rc = rk_classify_dbset(ctx, dbs, lr, pr, &br);
+    if (rc) return fail("classification");
+    for (size_t k = 0; k < ns && !rc; ++k) {
+      const rk_result r{order.data() + off[k], gid.data() + off[k], rep.data() + off[k], n_out[k],
+                        n_groups[k]};
+      if ((rc = rk_dbset_write_csv(dbs, (uint32_t)k, outs[k].c_str(), &r)))
+        std::fprintf(stderr, "writing %s failed (%d)\n", outs[k].c_str(), rc);
+    }
+    t2 = now_s();
+    if (rc) return fail("host save");
+  }
+  if (timing) {
+    rk_ingress_stats ing{};
+    rk_get_ingress_stats(ctx, &ing);
+    rk_batch_stats bs{};
+    rk_get_batch_stats(ctx, &bs);
+    rk_egress_stats eg{};
+    rk_get_egress_stats(ctx, &eg);
+    std::fprintf(stderr,
+                 "{\"sets\": %zu, \"frags\": %llu, \"load_s\": %.6f, \"classify_save_s\": %.6f, "
+                 "\"ingress\": {\"body_bytes\": %llu, \"lines\": %llu, \"accepted\": %llu, "
+                 "\"host_lines\": %llu, \"windows\": %u, \"h2d_ms\": %.3f, \"device_ms\": %.3f, "
+                 "\"host_fix_ms\": %.3f, \"d2h_ms\": %.3f, \"total_ms\": %.3f}, "
+                 "\"batch\": {\"sub_batches\": %u, \"looped_sets\": %u, \"batched_sets\": %u, "
+                 "\"device_ms\": %.3f}, "
+                 "\"egress\": {\"rows\": %llu, \"bytes\": %llu, \"host_rows\": %llu, "
+                 "\"chunks\": %u, \"upload_ms\": %.3f, \"device_ms\": %.3f, "
+                 "\"host_fix_ms\": %.3f, \"d2h_write_ms\": %.3f, \"total_ms\": %.3f}}\n",
+                 ns, (unsigned long long)n, t1 - t0, t2 - t1, (unsigned long long)ing.body_bytes,
+                 (unsigned long long)ing.lines, (unsigned long long)ing.accepted,
+                 (unsigned long long)ing.host_lines, ing.windows, ing.h2d_ms, ing.device_ms,
+                 ing.host_fix_ms, ing.d2h_ms, ing.total_ms, bs.sub_batches, bs.looped_sets,
+                 bs.batched_sets, bs.device_ms, (unsigned long long)eg.rows,
+                 (unsigned long long)eg.bytes, (unsigned long long)eg.host_rows, eg.chunks,
+                 eg.upload_ms, eg.device_ms, eg.host_fix_ms, eg.d2h_write_ms, eg.total_ms);
+  }
+  rk_dbset_free(dbs);
+  rk_destroy(ctx);
+  std::printf("Repkiller finished with no errors\n");
+  return 0;
+}
+
+// --batch: every listed CSV through one batched classification
+static int run_batch(const char *list_path, double lr, double pr, int device) {
+  std::vector<std::string> ins, outs;
+  if (!read_batch_list(list_path, ins, outs)) return 1;
   const size_t ns = ins.size();
   std::printf("--- Running REPKILLER (MI355X), %zu fragment sets ---\n\n", ns);
   std::fflush(stdout);
@@ -246,8 +350,8 @@ int main(int argc, char **argv) {
     print_help();
     return 1;
   }
-  if (device_parse && (soa_in || batch_list || gpus != 1)) {
-    std::fprintf(stderr, "--device-parse does not combine with --soa, --batch or --gpus.\n");
+  if (device_parse && (soa_in || gpus != 1)) {
+    std::fprintf(stderr, "--device-parse does not combine with --soa or --gpus.\n");
     print_help();
     return 1;
   }
@@ -264,6 +368,7 @@ int main(int argc, char **argv) {
       print_help();
       return 1;
     }
+    if (device_parse) return run_batch_device(batch_list, lr, pr, device, device_save, timing);
     return run_batch(batch_list, lr, pr, device);
   }
   const bool local = comm_kind ? !std::strcmp(comm_kind, "local") : same_device;

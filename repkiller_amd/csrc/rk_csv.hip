@@ -23,6 +23,16 @@
 // resident columns are an allocation of the database's own, so no later
 // rk_classify* on the context can alias them.
 //
+// A batch of files (rk_dbset_load_csv_device) runs the same four steps over
+// ONE byte stream: every file is mapped, its header read on the host, and the
+// bodies are gathered piece by piece into the staging slots (io_h2d_gather), a
+// body without a final newline getting one, so no line joins the next file's
+// first.  Windows cut the stream as they cut one body, inside a set or at a set
+// boundary.  After each window's compaction one lane per set whose body starts
+// in the window finds the set's first row (k_csv_setoff); the per-set count
+// check (FragmentsDatabase.cpp:99) runs on those offsets before the columns
+// come down into the one combined rk_db of the rk_dbset.
+//
 // The load is synchronous: it returns when the host columns are complete.
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -228,7 +238,42 @@ __global__ __launch_bounds__(TB) void k_csv_scatter(const uint8_t *status, uint6
   d.sim[o] = s.sim[i], d.strand[o] = s.strand[i];
 }
 
+// A batch of files: set k's first row in the combined columns.  Lane k takes a
+// set whose body starts in this window at stream offset first[k] (a line start:
+// every body ends in a newline there).  It lower-bounds that offset in start[],
+// then adds the line's block prefix and the accepted lines before it in its
+// 256-line block: no atomics, and the work scales with the sets, not the lines.
+__global__ __launch_bounds__(TB) void k_csv_setoff(const uint64_t *first, uint32_t ns,
+                                                  const uint64_t *start, uint64_t lines,
+                                                  const uint8_t *status, const uint64_t *blk_pre,
+                                                  uint64_t out_base, uint64_t *set_off) {
+  const uint32_t k = blockIdx.x * TB + threadIdx.x;
+  if (k >= ns) return;
+  const uint64_t f = first[k];
+  // (the host passes only sets with wbase <= f < wbase + W, and f is the start
+  // of one of the window's lines, so the search ends at lo < lines)
+  uint64_t lo = 0, hi = lines;
+  while (lo < hi) {
+    const uint64_t mid = lo + (hi - lo) / 2;
+    if (start[mid] < f) lo = mid + 1;
+    else hi = mid;
+  }
+  uint64_t rows = blk_pre[lo / TB];
+  for (uint64_t i = lo - lo % TB; i < lo; ++i) rows += status[i] == rk::CSV_ACCEPT;
+  set_off[k] = out_base + rows;
+}
+
 // ------------------------------------------------------------------ host --
+
+using Stream = rk::CsvStream;  // rk_csv_stream.h
+
+// the sets of a batch: where each body starts in the stream, and its first row
+struct SetIndex {
+  std::vector<uint64_t> first;    // nsets: stream offset of set k's body
+  std::vector<uint64_t> host_off; // nsets: first row where the host decided it (~0: not)
+  std::vector<uint64_t> total;    // nsets: the header totals
+  uint64_t *d_first = nullptr, *d_off = nullptr;  // device: first[], first rows (~0: not set)
+};
 
 struct Mapped {
   const char *p = nullptr;
@@ -317,11 +362,13 @@ int size_columns(rk_db *db, uint64_t n) {
 
 struct Load {
   rk_ctx *ctx;
-  const char *body;  // the mapped body; offsets below are relative to it
+  const Stream *body;  // the body bytes; offsets below are relative to the stream
   Cols fin;          // final device columns, out_cap rows
   uint64_t out_cap, total_hdr;
   uint64_t out_n = 0;  // rows in the final columns so far
   rk_ingress_stats *st;
+  SetIndex *sets = nullptr;  // a batch of files: per-set first rows are kept
+  bool overflow = false;     // a batch: more rows than out_cap (some set exceeds its total)
   Events ev;
 
   int timed_begin() {
@@ -345,6 +392,12 @@ struct Load {
     const uint64_t k = rows.size();
     if (!k) return RK_OK;
     if (out_n + k > total_hdr) return RK_E_COUNT;
+    if (sets && out_n + k > out_cap) {  // the per-set count check names the set
+      overflow = true;
+      out_n += k;
+      rows.clear();
+      return RK_OK;
+    }
     std::vector<uint64_t> u(k);
     std::vector<float> f(k);
     std::vector<uint8_t> b(k);
@@ -391,7 +444,14 @@ struct Load {
     carve_a(ra, &raw, &tile_cnt, &tile_pre, &cnt);
 
     double t = rk::wall_ms();
-    if ((rc = rk::io_h2d(ctx, {{(void *)(body + wbase), raw, (size_t)W}}))) return rc;
+    // (one piece with nothing appended is its own bytes: the plain upload.  A
+    // one-file batch whose body got a newline is a stream like any other: its
+    // last byte is not in the file)
+    if (body->p.size() == 1 && !body->nl[0])
+      rc = rk::io_h2d(ctx, {{(void *)(body->p[0] + wbase), raw, (size_t)W}});
+    else
+      rc = rk::io_h2d_gather(ctx, body->io(), wbase, W, raw);
+    if (rc) return rc;
     st->h2d_ms += rk::wall_ms() - t;
 
     if ((rc = timed_begin())) return rc;
@@ -402,7 +462,7 @@ struct Load {
     HIPCHK(ctx, hipMemcpyAsync(ctx->host, tile_pre + ntiles, 8, hipMemcpyDeviceToHost, s));
     if ((rc = timed_end())) return rc;
     std::memcpy(&newlines, ctx->host, 8);
-    const uint32_t tail = body[wbase + W - 1] != '\n';
+    const uint32_t tail = body->at(wbase + W - 1) != '\n';
     const uint64_t lines = newlines + tail;
     if (newlines > W) {
       ctx->err = "csv line index: more newlines than bytes";
@@ -473,8 +533,13 @@ struct Load {
             outside = true;
             continue;
           }
+          const char *text = body->span(off, len);
+          if (!text) {
+            outside = true;
+            continue;
+          }
           rk::DbRow r;
-          if (rk::db_parse_line(body + off, body + off + len, &r)) {
+          if (rk::db_parse_line(text, text + len, &r)) {
             q.xs = r.xs, q.ys = r.ys, q.xe = r.xe, q.ye = r.ye, q.len = r.len, q.score = r.score;
             q.ident = r.ident, q.sim = r.sim, q.strand = r.strand;
             q.status = rk::CSV_ACCEPT;
@@ -515,8 +580,11 @@ struct Load {
     // count check (FragmentsDatabase.cpp:99), then the stable compaction
     if (out_n + accepted > total_hdr) return RK_E_COUNT;
     if (out_n + accepted > out_cap) {
-      ctx->err = "csv compaction: more rows than the bound on accepted lines";
-      return RK_E_INTERNAL;
+      if (!sets) {
+        ctx->err = "csv compaction: more rows than the bound on accepted lines";
+        return RK_E_INTERNAL;
+      }
+      overflow = true;  // (the scatter stops at out_cap; the per-set check names the set)
     }
     if (lines) {
       if ((rc = timed_begin())) return rc;
@@ -524,6 +592,15 @@ struct Load {
       rk::k_csv_scan<uint64_t><<<1, 1024, 0, s>>>(blk_cnt, nblk, blk_pre);
       k_csv_scatter<<<(uint32_t)nblk, TB, 0, s>>>(status, lines, blk_pre, out_n, out_cap, stg,
                                                   fin);
+      if (sets) {  // the sets whose bodies start in this window
+        const auto &f = sets->first;
+        const size_t k0 = (size_t)(std::lower_bound(f.begin(), f.end(), wbase) - f.begin());
+        const size_t k1 = (size_t)(std::lower_bound(f.begin(), f.end(), wbase + W) - f.begin());
+        if (k1 > k0)
+          k_csv_setoff<<<grid_for(k1 - k0), TB, 0, s>>>(sets->d_first + k0, (uint32_t)(k1 - k0),
+                                                        start, lines, status, blk_pre, out_n,
+                                                        sets->d_off + k0);
+      }
       if ((rc = timed_end())) return rc;
     }
     out_n += accepted;
@@ -532,29 +609,30 @@ struct Load {
   }
 };
 
-int load_device(rk_ctx *ctx, const char *path, uint32_t flags, rk_db **out) {
-  const double t0 = rk::wall_ms();
-  rk_ingress_stats &st = ctx->ingress;
-  st = rk_ingress_stats{};
-  Mapped m;
-  m.fd = open(path, O_RDONLY);
-  if (m.fd < 0) return RK_E_IO;
+int map_file(const char *path, Mapped *m) {
+  m->fd = open(path, O_RDONLY);
+  if (m->fd < 0) return RK_E_IO;
   struct stat sb;
-  if (fstat(m.fd, &sb) != 0) return RK_E_IO;
-  m.n = (size_t)sb.st_size;
-  if (m.n) {
-    void *q = mmap(nullptr, m.n, PROT_READ, MAP_PRIVATE, m.fd, 0);
+  if (fstat(m->fd, &sb) != 0) return RK_E_IO;
+  m->n = (size_t)sb.st_size;
+  if (m->n) {
+    void *q = mmap(nullptr, m->n, PROT_READ, MAP_PRIVATE, m->fd, 0);
     if (q == MAP_FAILED) return RK_E_IO;
-    m.p = (const char *)q;
+    m->p = (const char *)q;
   }
-  std::unique_ptr<rk_db, void (*)(rk_db *)> db(new (std::nothrow) rk_db, rk_db_free);
-  if (!db) return RK_E_NOMEM;
-  const char *end = m.p + m.n;
-  bool eof = false;
-  const char *p = rk::db_read_header(db.get(), m.p, end, &eof);
-  const uint64_t body_bytes = (!eof && p < end) ? (uint64_t)(end - p) : 0;
-  st.body_bytes = body_bytes;
+  return RK_OK;
+}
 
+// The body bytes through the device into db's nine host columns and, where
+// flags keep them, its resident ones.  total_hdr: the bound of the count check
+// on the rows as a whole (a batch checks per set afterwards: ~0); row_bound: a
+// bound on the rows the final columns must hold.  sets: a batch's set index,
+// whose per-set first rows come back in sets->host_off (every entry set) after
+// the per-set count check.
+int load_body(rk_ctx *ctx, const Stream &body, uint32_t flags, rk_db *db, uint64_t total_hdr,
+              uint64_t row_bound, SetIndex *sets) {
+  rk_ingress_stats &st = ctx->ingress;
+  const uint64_t body_bytes = body.size();
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const bool keep = flags & RK_DB_KEEP_DEVICE;
   const bool keep_rows = flags == RK_DB_KEEP_ROWS;
@@ -566,7 +644,18 @@ int load_device(rk_ctx *ctx, const char *path, uint32_t flags, rk_db **out) {
   uint64_t n = 0;
   if (body_bytes) {
     // an accepted line holds at least "Frag,1": 6 bytes and its newline
-    const uint64_t cap = std::min<uint64_t>(db->total_hdr, body_bytes / 7 + 1);
+    const uint64_t cap = std::min<uint64_t>(row_bound, body_bytes / 7 + 1);
+    const size_t ns = sets ? sets->first.size() : 0;
+    DevBuf set_tab;
+    if (sets) {
+      int rc0 = dev_alloc(ctx, &set_tab.p, ns * 16, "csv set index");
+      if (rc0) return rc0;
+      sets->d_first = (uint64_t *)set_tab.p, sets->d_off = sets->d_first + ns;
+      HIPCHK(ctx, hipMemcpyAsync(sets->d_first, sets->first.data(), ns * 8, hipMemcpyHostToDevice,
+                                 ctx->stream));
+      HIPCHK(ctx, hipMemsetAsync(sets->d_off, 0xFF, ns * 8, ctx->stream));
+      HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    }
     // the database's own columns: x_start, y_start, length, strand (kept with
     // RK_DB_KEEP_DEVICE) and the five others
     // (with RK_DB_KEEP_ROWS one allocation holds both blocks, the five others
@@ -580,14 +669,15 @@ int load_device(rk_ctx *ctx, const char *path, uint32_t flags, rk_db **out) {
     if ((rc = dev_alloc(ctx, &kept.p, pk.off + (keep_rows ? pr.off : 0), "csv columns"))) return rc;
     if (!keep_rows && (rc = dev_alloc(ctx, &rest.p, pr.off, "csv columns"))) return rc;
     rk::Carve ck{(char *)kept.p}, cr{keep_rows ? (char *)kept.p + pk.off : (char *)rest.p};
-    Load L{ctx, p};
+    Load L{ctx, &body};
+    L.sets = sets;
     L.fin.xs = ck.take<uint64_t>(cap), L.fin.ys = ck.take<uint64_t>(cap);
     L.fin.len = ck.take<uint64_t>(cap), L.fin.strand = ck.take<uint8_t>(cap);
     L.fin.xe = cr.take<uint64_t>(cap), L.fin.ye = cr.take<uint64_t>(cap);
     L.fin.score = cr.take<uint64_t>(cap), L.fin.ident = cr.take<uint64_t>(cap);
     L.fin.sim = cr.take<float>(cap);
     L.out_cap = cap;
-    L.total_hdr = db->total_hdr;
+    L.total_hdr = total_hdr;
     L.st = &st;
     HIPCHK(ctx, hipEventCreate(&L.ev.a));
     HIPCHK(ctx, hipEventCreate(&L.ev.b));
@@ -600,8 +690,8 @@ int load_device(rk_ctx *ctx, const char *path, uint32_t flags, rk_db **out) {
     while (pos < body_bytes) {
       uint64_t wend = body_bytes;
       if (body_bytes - pos > wmax) {
-        const void *nl = memrchr(p + pos, '\n', (size_t)wmax);
-        wend = nl ? (uint64_t)((const char *)nl - p) + 1 : pos;
+        const uint64_t nl = body.last_nl(pos, pos + wmax);
+        wend = nl != ~0ull ? nl + 1 : pos;
       }
       if (wend > pos) {
         if ((rc = L.flush_rows(pending))) return rc;
@@ -610,22 +700,59 @@ int load_device(rk_ctx *ctx, const char *path, uint32_t flags, rk_db **out) {
         continue;
       }
       const double t = rk::wall_ms();
-      const char *nl = (const char *)std::memchr(p + pos, '\n', (size_t)(body_bytes - pos));
-      const uint64_t le = nl ? (uint64_t)(nl - p) : body_bytes;
+      if (sets)  // the sets whose bodies start with this line: the host knows their first row
+        for (size_t k = (size_t)(std::lower_bound(sets->first.begin(), sets->first.end(), pos) -
+                                 sets->first.begin());
+             k < ns && sets->first[k] == pos; ++k)
+          sets->host_off[k] = L.out_n + pending.size();
+      const uint64_t nl = body.next_nl(pos);
+      const uint64_t le = nl != ~0ull ? nl : body_bytes;
+      const char *text = body.span(pos, le - pos);
+      if (!text) {
+        ctx->err = "csv host line: a line crosses two files' bodies";
+        return RK_E_INTERNAL;
+      }
       rk::DbRow r;
-      if (rk::db_parse_line(p + pos, p + le, &r)) pending.push_back(r);
+      if (rk::db_parse_line(text, text + (le - pos), &r)) pending.push_back(r);
       ++st.lines;
       ++st.host_lines;
-      pos = nl ? le + 1 : body_bytes;
+      pos = nl != ~0ull ? le + 1 : body_bytes;
       st.host_fix_ms += rk::wall_ms() - t;
-      if (L.out_n + pending.size() > db->total_hdr) return RK_E_COUNT;
+      if (L.out_n + pending.size() > total_hdr) return RK_E_COUNT;
     }
     if ((rc = L.flush_rows(pending))) return rc;
     n = L.out_n;
+    if (sets) {
+      // first rows: the device's where a window held the body's start, the
+      // host's where a host line did, the row count for bodies at the stream's end
+      std::vector<uint64_t> got(ns);
+      HIPCHK(ctx, hipMemcpy(got.data(), sets->d_off, ns * 8, hipMemcpyDeviceToHost));
+      for (size_t k = 0; k < ns; ++k)
+        if (sets->host_off[k] == ~0ull) sets->host_off[k] = got[k] != ~0ull ? got[k] : n;
+      sets->d_first = sets->d_off = nullptr;
+      // the count check (FragmentsDatabase.cpp:99), per file, before any row is
+      // promised to anyone
+      for (size_t k = 0; k < ns; ++k) {
+        const uint64_t a = sets->host_off[k], b = k + 1 < ns ? sets->host_off[k + 1] : n;
+        if (a > b) {
+          ctx->err = "csv set index: first rows decrease at set " + std::to_string(k);
+          return RK_E_INTERNAL;
+        }
+        if (b - a > sets->total[k]) {
+          ctx->err = "set " + std::to_string(k) + ": more fragments than the header total";
+          return RK_E_COUNT;
+        }
+      }
+      if (L.overflow) {
+        ctx->err = "csv compaction: more rows than the sets' header totals allow";
+        return RK_E_INTERNAL;
+      }
+      if (n >= 0xFFFFFFFFull) return RK_E_TOO_MANY;
+    }
 
     // the nine columns into the database's vectors
     const double t = rk::wall_ms();
-    if ((rc = size_columns(db.get(), n))) return rc;
+    if ((rc = size_columns(db, n))) return rc;
     if ((rc = rk::io_d2h(ctx, {{db->x_start.data(), L.fin.xs, n * 8},
                                {db->y_start.data(), L.fin.ys, n * 8},
                                {db->x_end.data(), L.fin.xe, n * 8},
@@ -649,8 +776,87 @@ int load_device(rk_ctx *ctx, const char *path, uint32_t flags, rk_db **out) {
     }
   }
   st.accepted = n;
+  return RK_OK;
+}
+
+int load_device(rk_ctx *ctx, const char *path, uint32_t flags, rk_db **out) {
+  const double t0 = rk::wall_ms();
+  rk_ingress_stats &st = ctx->ingress;
+  st = rk_ingress_stats{};
+  Mapped m;
+  int rc = map_file(path, &m);
+  if (rc) return rc;
+  std::unique_ptr<rk_db, void (*)(rk_db *)> db(new (std::nothrow) rk_db, rk_db_free);
+  if (!db) return RK_E_NOMEM;
+  const char *end = m.p + m.n;
+  bool eof = false;
+  const char *p = rk::db_read_header(db.get(), m.p, end, &eof);
+  const uint64_t body_bytes = (!eof && p < end) ? (uint64_t)(end - p) : 0;
+  st.body_bytes = body_bytes;
+  Stream body;
+  body.add(p, body_bytes, false);
+  if ((rc = load_body(ctx, body, flags, db.get(), db->total_hdr, db->total_hdr, nullptr)))
+    return rc;
   st.total_ms = rk::wall_ms() - t0;
   *out = db.release();
+  return RK_OK;
+}
+
+// Every listed file mapped (descriptors closed as the work goes: a mapping does
+// not need its own), its header read on the host, and the bodies parsed as one
+// stream into one combined database.
+int load_set(rk_ctx *ctx, const char *const *paths, uint32_t nsets, uint32_t flags,
+             rk_dbset **out) {
+  const double t0 = rk::wall_ms();
+  rk_ingress_stats &st = ctx->ingress;
+  st = rk_ingress_stats{};
+  std::unique_ptr<rk_dbset, void (*)(rk_dbset *)> dbs(new (std::nothrow) rk_dbset,
+                                                      rk_dbset_free);
+  if (!dbs) return RK_E_NOMEM;
+  dbs->db = new rk_db;
+  std::vector<Mapped> maps(nsets);
+  Stream body;
+  SetIndex sets;
+  dbs->set_off.assign((size_t)nsets + 1, 0);
+  dbs->len_x_hdr.resize(nsets), dbs->len_y_hdr.resize(nsets), dbs->total_hdr.resize(nsets);
+  dbs->header.resize(nsets);
+  uint64_t bound = 0;
+  for (uint32_t k = 0; k < nsets; ++k) {
+    Mapped &m = maps[k];
+    const int rc = map_file(paths[k], &m);
+    if (m.fd >= 0) close(m.fd);
+    m.fd = -1;
+    if (rc) {
+      ctx->err = "set " + std::to_string(k) + ": cannot open or map " + paths[k];
+      return rc;
+    }
+    rk_db hdr;
+    bool eof = false;
+    const char *end = m.p + m.n;
+    const char *p = rk::db_read_header(&hdr, m.p, end, &eof);
+    const uint64_t len = (!eof && p < end) ? (uint64_t)(end - p) : 0;
+    dbs->header[k].swap(hdr.header);
+    dbs->len_x_hdr[k] = hdr.len_x_hdr, dbs->len_y_hdr[k] = hdr.len_y_hdr;
+    dbs->total_hdr[k] = hdr.total_hdr;
+    if (__builtin_add_overflow(bound, hdr.total_hdr, &bound)) bound = ~0ull;
+    sets.first.push_back(body.size());
+    // (a body that does not end in a newline gets one: getline yields the same
+    // lines, and its last line cannot join the next file's first)
+    body.add(p, len, len && p[len - 1] != '\n');
+    st.body_bytes += len;
+  }
+  sets.host_off.assign(nsets, ~0ull);
+  sets.total = dbs->total_hdr;
+  // (one row of slack: a set over its total must reach the per-set check, not
+  // the bound of the columns)
+  if (bound != ~0ull) ++bound;
+  const int rc = load_body(ctx, body, flags, dbs->db, ~0ull, bound, nsets ? &sets : nullptr);
+  if (rc) return rc;
+  const uint64_t n = dbs->db->x_start.size();
+  for (uint32_t k = 0; k < nsets; ++k) dbs->set_off[k] = body.size() ? sets.host_off[k] : 0;
+  dbs->set_off[nsets] = n;
+  st.total_ms = rk::wall_ms() - t0;
+  *out = dbs.release();
   return RK_OK;
 }
 
@@ -670,6 +876,45 @@ extern "C" int rk_db_load_csv_device(rk_ctx *ctx, const char *path, uint32_t fla
     ctx->err = "unexpected C++ exception";
     return RK_E_INTERNAL;
   }
+}
+
+extern "C" int rk_dbset_load_csv_device(rk_ctx *ctx, const char *const *paths, uint32_t nsets,
+                                        uint32_t flags, rk_dbset **out) {
+  if (!ctx || !out || (nsets && !paths) || (flags & ~(uint32_t)RK_DB_KEEP_ROWS) || flags == 2)
+    return RK_E_ARG;
+  for (uint32_t k = 0; k < nsets; ++k)
+    if (!paths[k]) return RK_E_ARG;
+  *out = nullptr;
+  ctx->err.clear();
+  try {
+    return load_set(ctx, paths, nsets, flags, out);
+  } catch (const std::bad_alloc &) {
+    ctx->err = "rk_dbset_load_csv_device: out of host memory";
+    return RK_E_NOMEM;
+  } catch (...) {
+    ctx->err = "unexpected C++ exception";
+    return RK_E_INTERNAL;
+  }
+}
+
+extern "C" void rk_dbset_free(rk_dbset *dbs) {
+  if (!dbs) return;
+  rk_db_free(dbs->db);
+  delete dbs;
+}
+
+extern "C" int rk_dbset_view(const rk_dbset *dbs, uint32_t *nsets, const uint64_t **set_off,
+                             const uint64_t **len_x_hdr, const uint64_t **len_y_hdr,
+                             const uint64_t **total_hdr, rk_frags_soa *host, rk_frags_soa *dev) {
+  if (!dbs) return RK_E_ARG;
+  if (dev && rk_db_device_view(dbs->db, dev)) return RK_E_ARG;
+  if (nsets) *nsets = (uint32_t)dbs->header.size();
+  if (set_off) *set_off = dbs->set_off.data();
+  if (len_x_hdr) *len_x_hdr = dbs->len_x_hdr.data();
+  if (len_y_hdr) *len_y_hdr = dbs->len_y_hdr.data();
+  if (total_hdr) *total_hdr = dbs->total_hdr.data();
+  if (host) (void)rk_db_view(dbs->db, host, nullptr, nullptr, nullptr);
+  return RK_OK;
 }
 
 extern "C" int rk_get_ingress_stats(const rk_ctx *ctx, rk_ingress_stats *st) {

@@ -24,6 +24,14 @@
 // staging slots, each of which is pwritten from where the DMA left it
 // (rk::io_d2h_sink).  Scratch comes from ctx->ws; uploaded result arrays from
 // ctx->io.
+//
+// A batch of sets (rk_dbset_write_csv_device) runs the same chunks over the
+// slots of an rk_batch_result: k_outb_len takes the place of the length pass
+// (it finds each slot's set, turns a used slot into its combined row, gives an
+// unused one length 0), the other passes run unchanged on the combined rows, and
+// k_outb_cuts gives the text offset at which every set of the chunk starts.
+// The writers split each pinned slot at those cuts and pwrite every piece into
+// its own set's file (SetFiles).
 #include <fcntl.h>
 #include <unistd.h>
 
@@ -31,6 +39,7 @@
 #include <atomic>
 #include <cerrno>
 #include <cstdlib>
+#include <mutex>
 #include <new>
 
 #include "rk_csv_row.h"
@@ -104,6 +113,89 @@ __global__ __launch_bounds__(OB) void k_out_len(OCols c, uint64_t n, Res r, uint
     if (total) atomicAdd(&ctr->bytes, (unsigned long long)total);
     if (nh) atomicAdd(&ctr->host_rows, (unsigned long long)nh);
   }
+}
+
+// ---- a batch of sets (rk_dbset_write_csv_device): the result is in
+// rk_batch_result layout, set s owning slots [off[s], off[s] + n_out[s]) with
+// out_order local to the set; the slots up to off[s + 1] are unused (the rows
+// of the set's dropped last xStart/10 bucket)
+struct SetTab {
+  const uint64_t *off;    // nsets + 1
+  const uint64_t *n_out;  // nsets
+  uint32_t ns;
+};
+
+// the set of slot p < off[ns]: the last s with off[s] <= p (an empty set shares
+// its offset with the next one and is never the answer); lo: a set known to
+// start at or before p
+__device__ inline uint32_t set_of(const SetTab &s, uint32_t lo, uint64_t p) {
+  uint32_t hi = s.ns;
+  while (hi - lo > 1) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (s.off[mid] <= p) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// k_out_len for slots [k0, k0 + cnt) of a batch (r is the chunk's slice of the
+// result arrays).  A used slot becomes the combined row off[s] + out_order[p],
+// kept in crow[] for the passes that follow (k_out_hostlist, k_out_put take it
+// as their order array); an unused slot has length 0.  The wave's first slot is
+// searched at a wave-uniform address; a lane searches on only when its slot
+// lies past that set's end.
+__global__ __launch_bounds__(OB) void k_outb_len(OCols c, SetTab s, Res r, uint64_t k0,
+                                                uint32_t cnt, uint32_t *crow, uint8_t *len8,
+                                                uint8_t *hst, uint32_t *blk_tot, Ctr *ctr) {
+  __shared__ uint32_t lds[OB];
+  const uint32_t k = blockIdx.x * OB + threadIdx.x;
+  uint32_t len = 0;
+  bool host = false;
+  if (k < cnt) {
+    const uint64_t p = k0 + k;
+    uint32_t set = set_of(s, 0, k0 + (k & ~63u));
+    if (p >= s.off[set + 1]) set = set_of(s, set, p);
+    const uint64_t base = s.off[set], local = p - base;
+    uint32_t i = 0;
+    if (local < s.n_out[set]) {
+      const uint64_t o = r.order[k];
+      if (o >= s.off[set + 1] - base) {
+        atomicOr(&ctr->err, OERR_ORDER);
+      } else {
+        i = (uint32_t)(base + o);
+        const rk::OutRow row = gather(c, i);
+        host = rk::csv_row(row, r.gid[k], r.rep[k], nullptr, &len) == rk::ROW_HOST;
+        if (host) len = 0;
+      }
+    }
+    crow[k] = i;
+    len8[k] = (uint8_t)len;
+    hst[k] = host ? 1 : 0;
+  }
+  uint32_t total;
+  (void)rk::block_excl_scan<OB>(len, lds, &total);
+  const int nh = __syncthreads_count(host);
+  if (threadIdx.x == 0) {
+    blk_tot[blockIdx.x] = total;
+    if (total) atomicAdd(&ctr->bytes, (unsigned long long)total);
+    if (nh) atomicAdd(&ctr->host_rows, (unsigned long long)nh);
+  }
+}
+
+// cuts[j] = chunk-local text offset of the first slot of set ks + j, for the m
+// sets whose slots start in the chunk (or at its end, for the last chunk's
+// trailing empty sets): its block's offset plus the lengths before the slot in
+// its 128-row block.  One lane per set; the host splits the text at the cuts.
+__global__ __launch_bounds__(OB) void k_outb_cuts(const uint64_t *off, uint32_t ks, uint32_t m,
+                                                 uint64_t k0, uint32_t cnt, const uint8_t *len8,
+                                                 const uint32_t *blk_off, uint32_t *cuts) {
+  const uint32_t j = blockIdx.x * OB + threadIdx.x;
+  if (j >= m) return;
+  const uint64_t q = off[ks + j] - k0;
+  const uint32_t p = q < cnt ? (uint32_t)q : cnt;  // (blk_off has the chunk's total at its end)
+  uint32_t at = blk_off[p / OB];
+  for (uint32_t i = p - p % OB; i < p; ++i) at += len8[i];
+  cuts[j] = at;
 }
 
 // the ROW_HOST rows as (k, i, gid, rep); any order, cap entries at most
@@ -228,6 +320,7 @@ bool pwrite_all(int fd, const char *p, size_t len, uint64_t at) {
 struct Chunk {
   uint32_t cnt = 0;
   uint64_t bytes = 0;
+  uint32_t ks = 0, m = 0;  // a batch: the sets ks .. ks + m - 1 start in the chunk
 };
 
 struct Save {
@@ -244,19 +337,34 @@ struct Save {
   uint32_t *poff, *blk_tot, *blk_off;
   Ctr *ctr;
   uint32_t *perr;  // the put passes' error bits: cleared once, read once at the end
+  // a batch of sets (null / unused on the single route): the device tables, the
+  // host's set_off, the chunk's combined rows, and per text buffer the cuts
+  const uint64_t *hoff = nullptr;
+  SetTab tab{};
+  uint32_t *crow = nullptr, *cuts[2] = {};
+  uint32_t *hcuts[2] = {};  // pinned
 
-  void carve(rk::Carve &c, uint32_t R) {
+  void carve(rk::Carve &c, uint32_t R, uint32_t nsets = 0) {
     const uint32_t nb = (R + OB - 1) / OB;
     len8 = c.take<uint8_t>(R), hst = c.take<uint8_t>(R), poff = c.take<uint32_t>(R);
     blk_tot = c.take<uint32_t>(nb), blk_off = c.take<uint32_t>(nb + 1);
     ctr = c.take<Ctr>(1), perr = c.take<uint32_t>(1);
+    if (!nsets) return;
+    crow = c.take<uint32_t>(R);
+    cuts[0] = c.take<uint32_t>(nsets), cuts[1] = c.take<uint32_t>(nsets);
+    tab.off = c.take<uint64_t>((size_t)nsets + 1), tab.n_out = c.take<uint64_t>(nsets);
+    tab.ns = nsets;
+  }
+  // the chunk's slice of the result as the passes after the length pass read it
+  Res chunk_res(uint64_t k0) const {
+    return Res{hoff ? crow : res.order + k0, res.gid + k0, res.rep + k0};
   }
 
   // host rows of chunk [k0, k0 + cnt): list, format, upload, patch the lengths
   int fix_up(uint64_t k0, uint32_t cnt, uint32_t nhost, int par, uint64_t *added) {
     hipStream_t s = ctx->stream;
     const uint32_t nb = (cnt + OB - 1) / OB;
-    const Res r{res.order + k0, res.gid + k0, res.rep + k0};
+    const Res r = chunk_res(k0);
     Patch &p = patch[par];
     p.release();
     void *list = nullptr;
@@ -343,10 +451,14 @@ struct Save {
     hipStream_t s = ctx->stream;
     const int par = (int)(c & 1);
     const uint32_t nb = (cnt + OB - 1) / OB;
-    const Res r{res.order + k0, res.gid + k0, res.rep + k0};
+    const Res r = chunk_res(k0);
     HIPCHK(ctx, hipEventRecord(ev.e[0], s));
     HIPCHK(ctx, hipMemsetAsync(ctr, 0, sizeof(Ctr), s));
-    k_out_len<<<nb, OB, 0, s>>>(cols, n, r, cnt, len8, hst, blk_tot, ctr);
+    if (hoff)
+      k_outb_len<<<nb, OB, 0, s>>>(cols, tab, Res{res.order + k0, res.gid + k0, res.rep + k0}, k0,
+                                   cnt, crow, len8, hst, blk_tot, ctr);
+    else
+      k_out_len<<<nb, OB, 0, s>>>(cols, n, r, cnt, len8, hst, blk_tot, ctr);
     HIPCHK(ctx, hipMemcpyAsync(ctx->host, ctr, sizeof(Ctr), hipMemcpyDeviceToHost, s));
     HIPCHK(ctx, hipEventRecord(ev.e[1], s));
     HIPCHK(ctx, hipEventSynchronize(ev.e[1]));
@@ -376,6 +488,21 @@ struct Save {
     if (rc) return rc;
     HIPCHK(ctx, hipEventRecord(ev.e[2 + 2 * par], s));
     rk::k_csv_scan<uint32_t><<<1, 1024, 0, s>>>(blk_tot, nb, blk_off);
+    if (hoff) {
+      // the sets whose first slot lies in the chunk; the last chunk also takes
+      // the empty sets at the very end
+      const uint64_t *b = hoff, *e = hoff + tab.ns;
+      out->ks = (uint32_t)(std::lower_bound(b, e, k0) - b);
+      out->m = (k0 + cnt >= hoff[tab.ns] ? tab.ns
+                                         : (uint32_t)(std::lower_bound(b, e, k0 + cnt) - b)) -
+               out->ks;
+      if (out->m) {
+        k_outb_cuts<<<(out->m + OB - 1) / OB, OB, 0, s>>>(tab.off, out->ks, out->m, k0, cnt, len8,
+                                                          blk_off, cuts[par]);
+        HIPCHK(ctx, hipMemcpyAsync(hcuts[par], cuts[par], (size_t)out->m * 4,
+                                   hipMemcpyDeviceToHost, s));
+      }
+    }
     k_out_put<<<nb, OB, 0, s>>>(cols, r, cnt, len8, hst, poff, (const char *)patch[par].text,
                                 blk_off, (char *)ctx->txt[par], bytes, perr);
     HIPCHK(ctx, hipEventRecord(ev.e[3 + 2 * par], s));
@@ -498,7 +625,397 @@ int check_args(rk_ctx *ctx, const rk_db *db, const char *what) {
   return RK_OK;
 }
 
+// ---- a batch of sets: one text stream, split into the sets' files ----------
+
+// A set's part of a chunk's text: bytes [t0, t1) go to its file at base + (x - t0).
+struct Seg {
+  uint32_t set;
+  uint64_t t0, t1, base;
+  int fd;
+  uint64_t left;  // bytes of [t0, t1) not yet written
+  bool ends;      // the set's last slot lies in this chunk: close when left is 0
+};
+
+// The output files of a batch.  The writers of io_d2h_sink split every pinned
+// slot at the chunk's cuts and pwrite each piece at its file's offset (header
+// length plus the bytes earlier chunks wrote for the set).  A file is opened
+// by the first writer that reaches it, which also writes its header, and
+// closed by the one that writes its last byte, so the descriptors open at once
+// are bounded by the slots in flight, not by the sets.  A path that cannot be
+// opened does not stop the others: the lowest such set is kept in `bad`, sets
+// from it on are skipped, and every lower-numbered file is complete when the
+// chunk is.
+struct SetFiles {
+  const rk_dbset *dbs;
+  const char *const *paths;
+  std::mutex mu[32];      // segment i's descriptor and byte count: mu[i % 32]
+  std::vector<Seg> segs;  // the chunk's, in text order
+  std::atomic<uint32_t> bad{~0u};
+  std::atomic<bool> io_bad{false};
+  // the set whose text runs on into the next chunk, its descriptor, its bytes so far
+  uint32_t open_set = ~0u;
+  int open_fd = -1;
+  uint64_t open_bytes = 0;
+
+  ~SetFiles() {
+    for (Seg &g : segs)
+      if (g.fd >= 0) ::close(g.fd);
+    if (open_fd >= 0) ::close(open_fd);
+  }
+  // under the segment's mutex (or on the calling thread between chunks)
+  int open_file(uint32_t k) {
+    if (k >= bad) return -1;
+    const int fd = ::open(paths[k], O_WRONLY | O_CREAT | O_TRUNC, 0644);
+    if (fd < 0) {
+      for (uint32_t b = bad; k < b && !bad.compare_exchange_weak(b, k);) {
+      }
+      return -1;
+    }
+    if (!pwrite_all(fd, dbs->header[k].data(), dbs->header[k].size(), 0)) io_bad = true;
+    return fd;
+  }
+  void close_file(int fd) {
+    if (::close(fd) != 0) io_bad = true;
+  }
+  // a set without output rows: its header alone
+  void header_only(uint32_t k) {
+    const int fd = open_file(k);
+    if (fd >= 0) close_file(fd);
+  }
+
+  // the segments of chunk [k0, k0 + cnt): the set running on from the last
+  // chunk, then the m sets that start here at cuts[0 .. m); header-only files
+  // of the latter are written here
+  bool begin_chunk(const uint64_t *off, const uint64_t *n_out, uint64_t k0, uint32_t cnt,
+                   uint32_t ks, uint32_t m, const uint32_t *cuts, uint64_t bytes) {
+    segs.clear();
+    for (uint32_t j = 0; j < m; ++j)
+      if (cuts[j] > bytes || (j && cuts[j] < cuts[j - 1])) return false;
+    const uint64_t end = k0 + cnt;
+    if (ks > 0 && (ks == dbs->header.size() || off[ks] > k0) && n_out[ks - 1]) {
+      const uint32_t k = ks - 1;
+      const bool mine = open_set == k;
+      const uint64_t t1 = m ? cuts[0] : bytes;
+      segs.push_back(Seg{k, 0, t1, dbs->header[k].size() + (mine ? open_bytes : 0),
+                         mine ? open_fd : -1, t1, off[k + 1] <= end});
+    } else if (open_fd >= 0) {
+      close_file(open_fd);
+    }
+    open_set = ~0u, open_fd = -1;
+    for (uint32_t j = 0; j < m; ++j) {
+      const uint32_t k = ks + j;
+      const uint64_t t0 = cuts[j], t1 = j + 1 < m ? cuts[j + 1] : bytes;
+      if (!n_out[k]) {
+        header_only(k);
+        continue;
+      }
+      segs.push_back(Seg{k, t0, t1, dbs->header[k].size(), -1, t1 - t0, off[k + 1] <= end});
+    }
+    return true;
+  }
+
+  // a writer's slot: bytes [off, off + len) of the chunk's text
+  bool sink(const char *p, size_t len, size_t off) {
+    const uint64_t lo = off, hi = off + len;
+    size_t i = (size_t)(std::partition_point(segs.begin(), segs.end(),
+                                             [&](const Seg &g) { return g.t1 <= lo; }) -
+                        segs.begin());
+    for (; i < segs.size() && segs[i].t0 < hi; ++i) {
+      Seg &g = segs[i];
+      const uint64_t a = std::max(lo, g.t0), b = std::min(hi, g.t1);
+      if (a >= b) continue;
+      int fd;
+      {
+        std::lock_guard<std::mutex> lk(mu[i % 32]);
+        if (g.fd < 0) g.fd = open_file(g.set);
+        fd = g.fd;
+      }
+      if (fd >= 0 && !pwrite_all(fd, p + (a - lo), (size_t)(b - a), g.base + (a - g.t0)))
+        io_bad = true;
+      std::lock_guard<std::mutex> lk(mu[i % 32]);
+      g.left -= b - a;
+      if (g.left == 0 && g.ends && g.fd >= 0) {
+        close_file(g.fd);
+        g.fd = -1;
+      }
+    }
+    return !io_bad;
+  }
+
+  // after the chunk's last sink call: a set that ended here without text in
+  // this chunk is closed; the one that runs on keeps its descriptor
+  void end_chunk() {
+    for (size_t i = 0; i < segs.size(); ++i) {
+      Seg &g = segs[i];
+      if (g.ends || g.set >= bad) {
+        if (g.fd >= 0) close_file(g.fd);
+      } else {  // (only the last segment can run on)
+        open_set = g.set, open_fd = g.fd;
+        open_bytes = g.base - dbs->header[g.set].size() + (g.t1 - g.t0);
+      }
+      g.fd = -1;
+    }
+    segs.clear();
+  }
+};
+
+struct PinnedFree {
+  void *p = nullptr;
+  ~PinnedFree() {
+    if (p) (void)hipHostFree(p);
+  }
+};
+
+int set_io_error(rk_ctx *ctx, const SetFiles &f) {
+  const uint32_t k = f.bad;
+  if (k != ~0u) ctx->err = "set " + std::to_string(k) + ": cannot open " + f.paths[k];
+  return RK_E_IO;
+}
+
+int write_set_device(rk_ctx *ctx, const rk_dbset *dbs, const char *const *paths,
+                     const rk_batch_result *res, uint32_t flags) {
+  const double t0 = rk::wall_ms();
+  rk_egress_stats &st = ctx->egress;
+  st = rk_egress_stats{};
+  const rk_db *db = dbs->db;
+  const uint32_t ns = (uint32_t)dbs->header.size();
+  const uint64_t *off = dbs->set_off.data();
+  const uint64_t n = off[ns];  // rows = slots
+  uint64_t rows = 0;
+  for (uint32_t k = 0; k < ns; ++k) {
+    if (res->n_out[k] > off[k + 1] - off[k]) {
+      ctx->err = "set " + std::to_string(k) + ": n_out exceeds the set's rows";
+      return RK_E_ARG;
+    }
+    rows += res->n_out[k];
+  }
+  SetFiles files{dbs, paths};
+  auto finish = [&](int rc) -> int {
+    st.total_ms = rk::wall_ms() - t0;
+    if (rc) return rc;
+    if (files.bad != ~0u || files.io_bad) return set_io_error(ctx, files);
+    return RK_OK;
+  };
+  if (!rows) {  // no text at all: every file is its header
+    for (uint32_t k = 0; k < ns && files.bad == ~0u; ++k) files.header_only(k);
+    return finish(RK_OK);
+  }
+
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  Save S{ctx, db};
+  S.cols = OCols{db->dev_x,     db->dev_y,     db->dev_xe,  db->dev_ye,    db->dev_len,
+                 db->dev_score, db->dev_ident, db->dev_sim, db->dev_strand};
+  S.n = n;
+  S.st = &st;
+  S.hoff = off;
+  for (auto &e : S.ev.e) HIPCHK(ctx, hipEventCreate(&e));
+  PinnedFree pin;
+  HIPCHK(ctx, hipHostMalloc(&pin.p, (size_t)ns * 8, hipHostMallocDefault));
+  S.hcuts[0] = (uint32_t *)pin.p, S.hcuts[1] = S.hcuts[0] + ns;
+  int rc;
+  if (flags & RK_RES_DEVICE) {
+    S.res = Res{res->out_order, res->gid, res->repval};
+  } else {
+    const double t = rk::wall_ms();
+    rk::Carve pc{nullptr};
+    pc.take<uint32_t>(n), pc.take<uint32_t>(n), pc.take<uint8_t>(n);
+    if ((rc = rk::grow(ctx, &ctx->io, &ctx->io_cap, pc.off, "result upload"))) return rc;
+    rk::Carve c{(char *)ctx->io};
+    uint32_t *dord = c.take<uint32_t>(n), *dgid = c.take<uint32_t>(n);
+    uint8_t *drep = c.take<uint8_t>(n);
+    if ((rc = rk::io_h2d(ctx, {{res->out_order, dord, (size_t)n * 4},
+                               {res->gid, dgid, (size_t)n * 4},
+                               {res->repval, drep, (size_t)n}})))
+      return rc;
+    S.res = Res{dord, dgid, drep};
+    st.upload_ms = rk::wall_ms() - t;
+  }
+  const uint32_t R = (uint32_t)std::min<uint64_t>(chunk_rows(), n);
+  rk::Carve ps{nullptr};
+  S.carve(ps, R, ns);
+  if ((rc = rk::grow(ctx, &ctx->ws, &ctx->ws_cap, ps.off, "csv rows out"))) return rc;
+  rk::Carve cs{(char *)ctx->ws};
+  S.carve(cs, R, ns);
+
+  hipStream_t s = ctx->stream;
+  HIPCHK(ctx, hipMemcpyAsync((void *)S.tab.off, off, ((size_t)ns + 1) * 8, hipMemcpyHostToDevice, s));
+  HIPCHK(ctx, hipMemcpyAsync((void *)S.tab.n_out, res->n_out, (size_t)ns * 8,
+                             hipMemcpyHostToDevice, s));
+  HIPCHK(ctx, hipMemsetAsync(S.perr, 0, 4, s));
+  HIPCHK(ctx, hipStreamSynchronize(s));  // (the tables are pageable host memory)
+
+  const uint64_t nchunks = (n + R - 1) / R;
+  auto rows_of = [&](uint64_t c) { return (uint32_t)std::min<uint64_t>(R, n - c * R); };
+  // on any failure below the stream is drained before the patch buffers go
+  auto fail = [&](int code) {
+    (void)hipStreamSynchronize(s);
+    return finish(code);
+  };
+  Chunk cur, next;
+  if ((rc = S.format_chunk(0, 0, rows_of(0), &cur))) return fail(rc);
+  for (uint64_t c = 0; c < nchunks; ++c) {
+    const int par = (int)(c & 1);
+    if (c + 1 < nchunks && (rc = S.format_chunk(c + 1, (c + 1) * R, rows_of(c + 1), &next)))
+      return fail(rc);
+    const double t = rk::wall_ms();
+    // the chunk's cuts are down once its put pass is (all but the last chunk's
+    // already is: the next chunk's length pass ran behind it)
+    HIPCHK(ctx, hipEventSynchronize(S.ev.e[3 + 2 * par]));
+    if (!files.begin_chunk(off, res->n_out, c * R, cur.cnt, cur.ks, cur.m, S.hcuts[par],
+                           cur.bytes)) {
+      ctx->err = "csv cuts: the sets' text offsets do not lie in the chunk in order";
+      return fail(RK_E_INTERNAL);
+    }
+    rc = rk::io_d2h_sink(ctx, ctx->txt[par], (size_t)cur.bytes, S.ev.e[3 + 2 * par],
+                         [&](const char *p, size_t len, size_t o) { return files.sink(p, len, o); });
+    files.end_chunk();
+    st.d2h_write_ms += rk::wall_ms() - t;
+    if (rc == 1) rc = RK_OK;  // (io_bad says so)
+    if (rc) return fail(rc);
+    float ms = 0;
+    HIPCHK(ctx, hipEventElapsedTime(&ms, S.ev.e[2 + 2 * par], S.ev.e[3 + 2 * par]));
+    st.device_ms += ms;
+    S.patch[par].release();
+    st.bytes += cur.bytes;
+    ++st.chunks;
+    cur = next;
+    if (files.bad != ~0u || files.io_bad) return fail(RK_OK);
+  }
+  st.rows = rows;
+  if (files.open_fd >= 0) files.close_file(files.open_fd), files.open_fd = -1;
+  HIPCHK(ctx, hipMemcpyAsync(ctx->host, S.perr, 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(ctx, hipStreamSynchronize(s));
+  if (*ctx->host) {
+    ctx->err = "csv put pass: a block's text does not fit its place";
+    return finish(RK_E_INTERNAL);
+  }
+  return finish(RK_OK);
+}
+
+// rk_classify_device_batch on the set's resident columns into DEVICE result
+// arrays carved from ctx->io (zeroed first, as rk_classify_batch's are);
+// returns with the stream idle
+int dbset_classify_resident(rk_ctx *ctx, const rk_dbset *dbs, double len_ratio, double pos_ratio,
+                            rk_batch_result *dres) {
+  rk_frags_soa dv;
+  if (rk_db_device_view(dbs->db, &dv)) return RK_E_ARG;
+  const uint32_t ns = (uint32_t)dbs->header.size();
+  const size_t n = dv.n;
+  if (n >= 0xFFFFFFFFull) return RK_E_TOO_MANY;
+  rk::Carve pc{nullptr};
+  pc.take<uint32_t>(n), pc.take<uint32_t>(n), pc.take<uint8_t>(n);
+  int rc = rk::grow(ctx, &ctx->io, &ctx->io_cap, pc.off, "result staging");
+  if (rc) return rc;
+  rk::Carve c{(char *)ctx->io};
+  dres->out_order = c.take<uint32_t>(n), dres->gid = c.take<uint32_t>(n);
+  dres->repval = c.take<uint8_t>(n);
+  if (n) {
+    HIPCHK(ctx, hipMemsetAsync(dres->out_order, 0, n * 4, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(dres->gid, 0, n * 4, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(dres->repval, 0, n, ctx->stream));
+  }
+  const rk_batch_params bp{ns, dbs->set_off.data(), dbs->len_x_hdr.data(), dbs->len_y_hdr.data(),
+                           len_ratio, pos_ratio};
+  if ((rc = rk_classify_device_batch(ctx, &dv, &bp, dres))) return rc;
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  return RK_OK;
+}
+
+int check_set_args(rk_ctx *ctx, const rk_dbset *dbs, bool rows, const char *what) {
+  if (!dbs->db->dev_free || (rows && !dbs->db->dev_rows)) {
+    ctx->err = std::string(what) + ": the set was not loaded with " +
+               (rows ? "RK_DB_KEEP_ROWS" : "RK_DB_KEEP_DEVICE");
+    return RK_E_ARG;
+  }
+  if (dbs->db->dev_device != ctx->device) {
+    ctx->err = std::string(what) + ": the set's columns are on another device";
+    return RK_E_ARG;
+  }
+  return RK_OK;
+}
+
+template <class F>
+int guarded(rk_ctx *ctx, const char *what, F &&body) {
+  try {
+    return body();
+  } catch (const std::bad_alloc &) {
+    (void)hipStreamSynchronize(ctx->stream);
+    ctx->err = std::string(what) + ": out of host memory";
+    return RK_E_NOMEM;
+  } catch (...) {
+    (void)hipStreamSynchronize(ctx->stream);
+    ctx->err = "unexpected C++ exception";
+    return RK_E_INTERNAL;
+  }
+}
+
 }  // namespace
+
+extern "C" int rk_classify_dbset(rk_ctx *ctx, const rk_dbset *dbs, double len_ratio,
+                                 double pos_ratio, rk_batch_result *out) {
+  if (!ctx || !dbs || !out) return RK_E_ARG;
+  const uint32_t ns = (uint32_t)dbs->header.size();
+  const size_t n = dbs->set_off[ns];
+  if (ns && (!out->n_out || !out->n_groups)) return RK_E_ARG;
+  if (n && (!out->out_order || !out->gid || !out->repval)) return RK_E_ARG;
+  ctx->err.clear();
+  int rc = check_set_args(ctx, dbs, false, "rk_classify_dbset");
+  if (rc) return rc;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  return guarded(ctx, "rk_classify_dbset", [&]() -> int {
+    rk_batch_result dres{nullptr, nullptr, nullptr, out->n_out, out->n_groups};
+    int rc2 = dbset_classify_resident(ctx, dbs, len_ratio, pos_ratio, &dres);
+    if (rc2 || !n) return rc2;
+    return rk::io_d2h(ctx, {{out->out_order, dres.out_order, n * 4},
+                            {out->gid, dres.gid, n * 4},
+                            {out->repval, dres.repval, n}});
+  });
+}
+
+extern "C" int rk_dbset_write_csv_device(rk_ctx *ctx, const rk_dbset *dbs,
+                                         const char *const *paths, const rk_batch_result *res,
+                                         uint32_t flags) {
+  if (!ctx || !dbs || !res || (flags & ~(uint32_t)RK_RES_DEVICE)) return RK_E_ARG;
+  const uint32_t ns = (uint32_t)dbs->header.size();
+  if (ns && (!paths || !res->n_out)) return RK_E_ARG;
+  for (uint32_t k = 0; k < ns; ++k)
+    if (!paths[k]) return RK_E_ARG;
+  if (dbs->set_off[ns] && (!res->out_order || !res->gid || !res->repval)) {
+    bool any = false;
+    for (uint32_t k = 0; k < ns; ++k) any |= res->n_out[k] != 0;
+    if (any) return RK_E_ARG;
+  }
+  ctx->err.clear();
+  int rc = check_set_args(ctx, dbs, true, "rk_dbset_write_csv_device");
+  if (rc) return rc;
+  return guarded(ctx, "rk_dbset_write_csv_device",
+                 [&] { return write_set_device(ctx, dbs, paths, res, flags); });
+}
+
+extern "C" int rk_classify_dbset_to_csv(rk_ctx *ctx, const rk_dbset *dbs, double len_ratio,
+                                        double pos_ratio, const char *const *paths,
+                                        uint64_t *n_out, uint64_t *n_groups) {
+  if (!ctx || !dbs) return RK_E_ARG;
+  const uint32_t ns = (uint32_t)dbs->header.size();
+  if (ns && !paths) return RK_E_ARG;
+  for (uint32_t k = 0; k < ns; ++k)
+    if (!paths[k]) return RK_E_ARG;
+  ctx->err.clear();
+  int rc = check_set_args(ctx, dbs, true, "rk_classify_dbset_to_csv");
+  if (rc) return rc;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  return guarded(ctx, "rk_classify_dbset_to_csv", [&]() -> int {
+    std::vector<uint64_t> no(ns), ng(ns);
+    rk_batch_result dres{nullptr, nullptr, nullptr, no.data(), ng.data()};
+    int rc2 = dbset_classify_resident(ctx, dbs, len_ratio, pos_ratio, &dres);
+    if (rc2) return rc2;
+    for (uint32_t k = 0; k < ns; ++k) {
+      if (n_out) n_out[k] = no[k];
+      if (n_groups) n_groups[k] = ng[k];
+    }
+    return write_set_device(ctx, dbs, paths, &dres, RK_RES_DEVICE);
+  });
+}
 
 extern "C" int rk_db_write_csv_device(rk_ctx *ctx, const rk_db *db, const char *path,
                                       const rk_result *res, uint32_t flags) {

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/repkiller_amd.h"
+#include "rk_csv_stream.h"
 #include "rk_internal.h"
 
 namespace rk {
@@ -130,6 +131,11 @@ struct IoPiece {
 };
 int io_h2d(rk_ctx *ctx, const std::vector<IoPiece> &pieces);
 int io_d2h(rk_ctx *ctx, const std::vector<IoPiece> &pieces);
+// (rk_csv_stream.h: host pieces read as one byte stream)
+// stream bytes [a, a + bytes) to dev: the host threads gather every staging
+// slot from however many pieces it spans, so thousands of small pieces cost
+// one DMA per slot, not one each; returns when the last byte has landed
+int io_h2d_gather(rk_ctx *ctx, const IoStream &s, uint64_t a, uint64_t bytes, void *dev);
 // device -> consumer: `bytes` bytes at dev come down through the pinned slots
 // and each filled slot goes to sink(data, len, off) (off: the slot's offset in
 // the piece) on a writer pool of at most 4 threads; a slot is issued again only

@@ -27,6 +27,16 @@ struct rk_db {
   void (*dev_free)(void *block, int device) = nullptr;
 };
 
+// rk_dbset_load_csv_device: one database per listed file, held as one combined
+// database (its header text and header numbers are unused) plus what differs
+// per set.  Set k's rows are rows [set_off[k], set_off[k + 1]) of db's columns.
+struct rk_dbset {
+  rk_db *db = nullptr;
+  std::vector<uint64_t> set_off;  // nsets + 1
+  std::vector<uint64_t> len_x_hdr, len_y_hdr, total_hdr;
+  std::vector<std::string> header;
+};
+
 namespace rk {
 
 struct DbRow {

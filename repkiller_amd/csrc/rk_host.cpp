@@ -513,11 +513,14 @@ inline char *format_row(char *o, const rk_db *db, uint32_t i, uint64_t gid, unsi
   return o;
 }
 
-int write_csv(const rk_db *db, const char *path, const uint32_t *gid, const uint8_t *rep,
-               const uint32_t *order, uint64_t n_out) {
+// `header`, then output row k from row base + order[k] of db's columns, where
+// order[k] < n_rows (a whole database: its own header, base 0, all its rows; a
+// set of an rk_dbset: the set's header and its slice of the combined columns)
+int write_csv_rows(const rk_db *db, const std::string &header, uint64_t base, uint64_t n_rows,
+                   const char *path, const uint32_t *gid, const uint8_t *rep,
+                   const uint32_t *order, uint64_t n_out) {
   const int fd = ::open(path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
   if (fd < 0) return RK_E_IO;
-  const uint64_t n_rows = db->x_start.size();
   // every chunk of rows is formatted into its own buffer in parallel, then
   // the chunks are written in parallel at their prefix-sum offsets (pwrite)
   const uint64_t chunk = 1u << 16;
@@ -545,8 +548,8 @@ int write_csv(const rk_db *db, const char *path, const uint32_t *gid, const uint
       // keeps that many rows' cache misses in flight instead of one
       constexpr uint64_t PF = 12;
       auto prefetch_row = [&](uint64_t k) {
-        const uint32_t i = order[k];
-        if (i >= n_rows) return;
+        if (order[k] >= n_rows) return;
+        const uint64_t i = base + order[k];
         __builtin_prefetch(&db->x_start[i]);
         __builtin_prefetch(&db->y_start[i]);
         __builtin_prefetch(&db->x_end[i]);
@@ -565,7 +568,7 @@ int write_csv(const rk_db *db, const char *path, const uint32_t *gid, const uint
           bad = true;
           break;
         }
-        o = format_row(o, db, i, gid[k], rep[k]);
+        o = format_row(o, db, (uint32_t)(base + i), gid[k], rep[k]);
       }
       blen[c] = (size_t)(o - b0);
     }
@@ -581,7 +584,7 @@ int write_csv(const rk_db *db, const char *path, const uint32_t *gid, const uint
     return RK_E_ARG;
   }
   std::vector<uint64_t> off(n_chunks + 1);
-  off[0] = db->header.size();
+  off[0] = header.size();
   for (uint64_t c = 0; c < n_chunks; ++c) off[c + 1] = off[c] + blen[c];
   auto put = [fd](const char *p, size_t len, uint64_t at) {
     while (len) {
@@ -594,7 +597,7 @@ int write_csv(const rk_db *db, const char *path, const uint32_t *gid, const uint
     }
     return true;
   };
-  std::atomic<bool> ok{put(db->header.data(), db->header.size(), 0)};
+  std::atomic<bool> ok{put(header.data(), header.size(), 0)};
   next = 0;
   auto wr = [&]() {
     for (uint64_t c; (c = next.fetch_add(1)) < n_chunks;)
@@ -610,6 +613,11 @@ int write_csv(const rk_db *db, const char *path, const uint32_t *gid, const uint
   return ok ? RK_OK : RK_E_IO;
 }
 
+int write_csv(const rk_db *db, const char *path, const uint32_t *gid, const uint8_t *rep,
+              const uint32_t *order, uint64_t n_out) {
+  return write_csv_rows(db, db->header, 0, db->x_start.size(), path, gid, rep, order, n_out);
+}
+
 }  // namespace
 
 char *rk::db_format_row(const rk_db *db, uint32_t i, uint64_t gid, unsigned rep, char *o) {
@@ -620,6 +628,22 @@ extern "C" int rk_db_write_csv(const rk_db *db, const char *path, const rk_resul
   if (!db || !path || !res || (res->n_out && (!res->gid || !res->repval || !res->out_order)))
     return RK_E_ARG;
   return write_csv(db, path, res->gid, res->repval, res->out_order, res->n_out);
+}
+
+// The host save of set k of an rk_dbset: the set's slice of the combined host
+// columns under its own header, through the writer above (no copy).
+extern "C" int rk_dbset_write_csv(const rk_dbset *dbs, uint32_t k, const char *path,
+                                  const rk_result *res) {
+  if (!dbs || !path || !res || k >= dbs->header.size() ||
+      (res->n_out && (!res->gid || !res->repval || !res->out_order)))
+    return RK_E_ARG;
+  try {
+    const uint64_t a = dbs->set_off[k], b = dbs->set_off[k + 1];
+    return write_csv_rows(dbs->db, dbs->header[k], a, b - a, path, res->gid, res->repval,
+                          res->out_order, res->n_out);
+  } catch (...) {
+    return RK_E_NOMEM;
+  }
 }
 
 // ------------------------------------------------------------- SaverQueue --

@@ -322,6 +322,40 @@ int io_h2d(rk_ctx *ctx, const std::vector<IoPiece> &pieces) {
   return RK_OK;
 }
 
+// Host -> device for bytes [a, a + bytes) of a stream of host pieces
+// (rk_csv_stream.h): every slot is filled by the pool, each worker gathering
+// its share from the pieces it spans, then moved by one DMA.
+int io_h2d_gather(rk_ctx *ctx, const IoStream &s, uint64_t a, uint64_t bytes, void *dev) {
+  int rc = io_ready(ctx);
+  if (rc) return rc;
+  if (a + bytes > s.off[s.n]) {
+    ctx->err = "stream upload: range past the stream";
+    return RK_E_INTERNAL;
+  }
+  IoEngine &e = *ctx->ioe;
+  bool busy[NSLOT] = {};
+  int k = 0;
+  for (uint64_t off = 0; off < bytes; off += SLOT) {
+    const size_t len = (size_t)std::min<uint64_t>(SLOT, bytes - off);
+    if (busy[k]) HIPCHK(ctx, hipEventSynchronize(e.ev[k]));
+    char *slot = e.slot[k];
+    const size_t share =
+        std::max<size_t>((len + e.pool->size() - 1) / e.pool->size(), (size_t)1 << 20);
+    const std::function<void(int)> job = [&](int t) {
+      const size_t lo = (size_t)t * share;
+      if (lo < len) stream_fill(s, slot + lo, a + off + lo, a + off + std::min(len, lo + share));
+    };
+    if (len <= share) stream_fill(s, slot, a + off, a + off + len);
+    else e.pool->run(job);
+    HIPCHK(ctx, hipMemcpyAsync((char *)dev + off, slot, len, hipMemcpyHostToDevice, e.io));
+    HIPCHK(ctx, hipEventRecord(e.ev[k], e.io));
+    busy[k] = true;
+    k = (k + 1) % NSLOT;
+  }
+  HIPCHK(ctx, hipStreamSynchronize(e.io));
+  return RK_OK;
+}
+
 // Device -> host: the DMA of up to NSLOT chunks runs ahead of the host copies
 // out of the slots.
 int io_d2h(rk_ctx *ctx, const std::vector<IoPiece> &pieces) {
