@@ -366,7 +366,7 @@ struct NWork {
   uint32_t *astatus, *ystatus, *xcnt, *xoff;
   uint4 *Ra, *Rb, *yrec, *erec;
   rk::Csr cx, cy;
-  uint32_t *xpos, *xbits;
+  uint32_t *xbits;
   uint32_t *par, *isnew, *newrank, *tag, *otag, *mrow, *goff;  // (gids: the caller's array)
   uint64_t *reckey;
   void *gsort;
@@ -397,7 +397,6 @@ size_t carve_nw(Carve &c, uint64_t n1, uint32_t nbx, NWork &w) {
     cs->pk = c.take<uint2>(n);
     cs->nbd = c.take<uint8_t>(n);
   }
-  w.xpos = c.take<uint32_t>(n);
   w.xbits = c.take<uint32_t>(n / 32 + 2);
   w.par = c.take<uint32_t>(n);
   w.isnew = c.take<uint32_t>(n);
@@ -586,7 +585,7 @@ int classify_narrow(rk_ctx *ctx, const rk_frags_soa *in, const rk_params *prms, 
     return RK_OK;
   }
   ctx->nw_fell_back = false;
-  // every row packs: now the workspace (~190 B per row)
+  // every row packs: now the workspace (~186 B per row)
   if (!early && (rc = ensure_nw(ctx, pl.n, pl.nbx, w))) return rc;
   rk::ScanScratch ss{w.scan, w.scan_cap};
   const uint32_t m = ctx->host[rk::CW_KEPT - rk::RB_ORDER],
@@ -635,8 +634,7 @@ int classify_narrow(rk_ctx *ctx, const rk_frags_soa *in, const rk_params *prms, 
     HIPCHK(ctx, hipEventRecord(ctx->join, st2));
   }
   mark(ctx, RK_PH_GATHER);
-  rk::nw_x_chunks(w.Ra, m, pl.nbx, pl.max_x, maxlen, w.xoff, w.cx, w.xpos, w.erec, w.ctrl, cc.W,
-                  st);
+  rk::nw_x_chunks(w.Ra, m, pl.nbx, pl.max_x, maxlen, w.xoff, w.cx, w.erec, w.ctrl, cc.W, st);
   // a batch's combined set: the upward-probe guards per set (rk_batch.hip)
   if (ctx->batch_tables) rk::batch_nbd(*ctx->batch_tables, false, w.cx, m, pl.nbx, st);
   HIPCHK(ctx, hipGetLastError());
@@ -685,7 +683,8 @@ int classify_narrow(rk_ctx *ctx, const rk_frags_soa *in, const rk_params *prms, 
       rk::zero_regions(st, {{w.ctrl + rk::CW_OPEN_X, 2 * sizeof(uint32_t)},
                             {w.ctrl + rk::CW_PEND_X, 2 * rk::PEND_WORDS * sizeof(uint32_t)}});
     if (prof) mark(ctx, RK_PH_SWEEP_X);
-    // X decisions: hits' parents (X winner); the X states become a bitmask after
+    // X decisions: a hit's parent is its X winner, a miss' itself; the parent
+    // words become the X-hit bitmask after
     rk::Axis ax{w.cx.key, w.cx.ent, nullptr, nullptr, w.cx.state, nullptr, w.par,
                 w.cx.pk, w.cx.nbd, w.rlen_at, w.rbeg_at, m, pl.max_x, pq.len_ratio,
                 pq.pos_ratio};
@@ -696,7 +695,7 @@ int classify_narrow(rk_ctx *ctx, const rk_frags_soa *in, const rk_params *prms, 
       return rc;
     ctx->stats.x_sweeps = sweeps;
     if (prof) mark(ctx, RK_PH_SWEEP_Y);
-    rk::nw_x_bits(w.xpos, w.cx.state, m, w.xbits, st);
+    rk::nw_x_bits(w.par, m, w.xbits, st);
     if (q == 0 && attempt == 0 && y_overlap) {  // the Y sort's last pass writes the CSR and the Y states
       HIPCHK(ctx, hipStreamWaitEvent(st, ctx->join, 0));
       rk::nw_y_sort_tail(w.yrec, w.Rb, m, yd, w.yhist, w.ystatus, w.cy, pl.nby, pl.max_y,

@@ -451,8 +451,8 @@ void nw_y_sort_after_x(const uint4 *yrec, uint4 *tmp, uint32_t m, const NwDigits
                        uint64_t max_y, const uint32_t *xbits, hipStream_t st,
                        const uint4 *src0 = nullptr);
 void nw_x_chunks(const uint4 *R, uint32_t m, uint32_t nbx, uint64_t max_x, uint32_t maxlen,
-                 const uint32_t *xoff, Csr cx, uint32_t *xpos, uint4 *erec, uint32_t *ctrl,
-                 uint32_t W, hipStream_t st, const uint4 *halo = nullptr, uint32_t G = 0);
+                 const uint32_t *xoff, Csr cx, uint4 *erec, uint32_t *ctrl, uint32_t W,
+                 hipStream_t st, const uint4 *halo = nullptr, uint32_t G = 0);
 // the sharded driver (rk_shard_nw.h): the processing order of received 16-B
 // records (Y records numbered from `base`), digit histograms of records whose
 // key is their first word (minus sub), the member sort of received records
@@ -465,10 +465,10 @@ void nw_member_sort_recv(const void *recs, bool narrow_keys, uint32_t m, uint32_
                          const NwDigits &e, const uint32_t *ehist, uint32_t *status, uint4 *t0,
                          uint4 *t1, uint32_t *sgid, uint64_t *key, uint32_t *tag, uint32_t *mrow,
                          hipStream_t st);
-// X hits as a bitmask by processing index, from the resolved X axis (xpos[k] =
-// X position of fragment k); then the Y states: X hits sit in the Y lists
-void nw_x_bits(const uint32_t *xpos, const uint8_t *xstate, uint32_t m, uint32_t *bits,
-               hipStream_t st);
+// X hits as a bitmask by processing index, from the parent words of a closed
+// X axis that ran with Axis::xres == nullptr (bit k = par[k] != k; par: 16-B
+// aligned); then the Y states: X hits sit in the Y lists
+void nw_x_bits(const uint32_t *par, uint32_t m, uint32_t *bits, hipStream_t st);
 void nw_fill_y(const uint32_t *ent, const uint32_t *bits, uint8_t *state, uint32_t m,
                hipStream_t st);
 void nw_assign(const uint32_t *par, const uint32_t *newrank, uint32_t *gidp, uint32_t m,

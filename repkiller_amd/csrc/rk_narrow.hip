@@ -1045,7 +1045,6 @@ struct XChunkArgs {
   uint32_t nbx;
   const uint32_t *xoff;  // [2 nch] strand-major entry offsets, [nch + 1] owner row starts (+ m)
   Csr out;
-  uint32_t *xpos;        // X position of every fragment (processing index)
   uint2 *erk;            // member records (processing order): {file row, sort key low 32}
   uint32_t *ehi;         // ... and the sort key's high 32 bits
   uint32_t *ctrl;        // CW_WIDE_KEYS: some sort key >= 2^32
@@ -1178,22 +1177,57 @@ __global__ void __launch_bounds__(64 * XC_WAVES) k_nw_xchunk(XChunkArgs a) {
       a.out.pk[q] = make_uint2((uint32_t)xc, len);
       a.out.nbd[q] = nbd_code_nw(xc, a.max_x);
       a.out.state[q] = ST_UNKNOWN;
-      a.xpos[k] = q;
     }
   }
 }
 
-// X hits as a bitmask by processing index, a wave per 64 fragments (their X
-// positions are a narrow window of the X axis: the state reads stay local)
-__global__ void k_nw_x_bits(const uint32_t *__restrict__ xpos, const uint8_t *__restrict__ xstate,
-                            uint32_t m, uint32_t *__restrict__ bits) {
+// X hits as a bitmask by processing index, straight from the parent words.
+// A closed X axis run with Axis::xres == nullptr has sent every entry through
+// record_decision (rk_occupancy.hip), which wrote par[k] = winner (another
+// fragment, so != k) for a hit and par[k] = k for an entry that joins the
+// list: fragment k hit on X exactly when par[k] != k.  Words an earlier call,
+// pair or attempt left there (the roots pass' flagged ranks among them) are
+// all rewritten by then.
+// An attempt whose queued sweeps left the X axis open (known only at the
+// roots' readback, after which the attempt is repeated) leaves stale words
+// under its open entries, and their bits are arbitrary.  That is harmless: a
+// bit is only ever turned into a Y state, ST_ACTIVE or ST_UNKNOWN (DstCsr,
+// the segment kernel's CsrEmit via bit 31 of the record's third word,
+// k_nw_fill_y); no bit becomes an index, a count or a size, and the parent
+// word itself is compared here and never followed.  The Y sweeps then decide
+// entries that are in range whatever their states, and the result is dropped.
+// Layout: lane l of a wave takes four fragments per 16-B load, eight lanes
+// make one word; bit k & 31 of word k >> 5, bits at and above m zero, words
+// from (m + 31) / 32 on untouched.
+constexpr int XB_T = 256, XB_ROWS = 4, XB_TILE = XB_T * 4 * XB_ROWS;  // fragments per block
+__global__ void __launch_bounds__(XB_T) k_nw_x_bits(const uint32_t *__restrict__ par, uint32_t m,
+                                                    uint32_t *__restrict__ bits) {
   const uint32_t lane = threadIdx.x & 63;
-  for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k - lane < m;
-       k += gridDim.x * blockDim.x) {
-    const bool hit = k < m && xstate[xpos[k]] == ST_HIT;
-    const uint64_t b = __ballot(hit);
-    if (lane == 0) bits[k >> 5] = (uint32_t)b;
-    if (lane == 32 && k < m) bits[k >> 5] = (uint32_t)(b >> 32);
+  const uint32_t tile = blockIdx.x * XB_TILE;  // (m < 2^30: no overflow)
+  uint4 p[XB_ROWS];
+#pragma unroll
+  for (int r = 0; r < XB_ROWS; ++r) {
+    const uint32_t k = tile + r * (XB_T * 4) + threadIdx.x * 4;
+    // misses where there is no fragment
+    p[r] = make_uint4(k, k + 1, k + 2, k + 3);
+    if (k + 3 < m) {
+      p[r] = *reinterpret_cast<const uint4 *>(par + k);
+    } else {
+      if (k < m) p[r].x = par[k];
+      if (k + 1 < m) p[r].y = par[k + 1];
+      if (k + 2 < m) p[r].z = par[k + 2];
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < XB_ROWS; ++r) {
+    const uint32_t k = tile + r * (XB_T * 4) + threadIdx.x * 4;
+    uint32_t v = (uint32_t)(p[r].x != k) | (uint32_t)(p[r].y != k + 1) << 1 |
+                 (uint32_t)(p[r].z != k + 2) << 2 | (uint32_t)(p[r].w != k + 3) << 3;
+    v <<= 4 * (lane & 7);
+    v |= __shfl_xor(v, 1);
+    v |= __shfl_xor(v, 2);
+    v |= __shfl_xor(v, 4);
+    if ((lane & 7) == 0 && k < m) bits[k >> 5] = v;
   }
 }
 
@@ -2191,8 +2225,8 @@ void nw_x_count_add(const uint4 *halo, uint32_t G, const NwChunkCounts &cc, hipS
 }
 
 void nw_x_chunks(const uint4 *R, uint32_t m, uint32_t nbx, uint64_t max_x, uint32_t maxlen,
-                 const uint32_t *xoff, Csr cx, uint32_t *xpos, uint4 *erec, uint32_t *ctrl,
-                 uint32_t W, hipStream_t st, const uint4 *halo, uint32_t G) {
+                 const uint32_t *xoff, Csr cx, uint4 *erec, uint32_t *ctrl, uint32_t W,
+                 hipStream_t st, const uint4 *halo, uint32_t G) {
   if (!m) return;
   uint32_t lgW = 0;
   while ((1u << lgW) < W) ++lgW;
@@ -2200,21 +2234,20 @@ void nw_x_chunks(const uint4 *R, uint32_t m, uint32_t nbx, uint64_t max_x, uint3
   // the member records take the erec buffer (16 B per row) as two arrays
   uint2 *erk = reinterpret_cast<uint2 *>(erec);
   XChunkArgs a{RecView{halo, G, R}, m, W, lgW, nch, (maxlen / 2 + 9) / 10, max_x, nbx, xoff, cx,
-               xpos, erk, reinterpret_cast<uint32_t *>(erk + m), ctrl};
+               erk, reinterpret_cast<uint32_t *>(erk + m), ctrl};
   kt_begin(st, KID_NW_XCHUNK);
   k_nw_xchunk<<<(nch + XC_WAVES - 1) / XC_WAVES, 64 * XC_WAVES,
                 XC_WAVES * 2 * W * sizeof(uint32_t), st>>>(a);
-  // records in (+ halo), X entries (key, id, packed record, code, state), their
-  // positions by fragment and member records out
-  kt_end(st, KID_NW_XCHUNK, 16.0 * m + 22.0 * m + 12.0 * m);  // records in; X CSR + position out; member records ({row, key lo} + key hi)
+  // records in (+ halo), X entries (key, id, packed record, code, state) and
+  // member records out
+  kt_end(st, KID_NW_XCHUNK, 16.0 * m + 18.0 * m + 12.0 * m);  // records in; X CSR out; member records ({row, key lo} + key hi)
 }
 
-void nw_x_bits(const uint32_t *xpos, const uint8_t *xstate, uint32_t m, uint32_t *bits,
-               hipStream_t st) {
+void nw_x_bits(const uint32_t *par, uint32_t m, uint32_t *bits, hipStream_t st) {
   if (!m) return;
   kt_begin(st, KID_NW_XBITS);
-  k_nw_x_bits<<<grid_for(m, 256), 256, 0, st>>>(xpos, xstate, m, bits);
-  kt_end(st, KID_NW_XBITS, 5.0 * m);
+  k_nw_x_bits<<<(m + XB_TILE - 1) / XB_TILE, XB_T, 0, st>>>(par, m, bits);
+  kt_end(st, KID_NW_XBITS, 4.125 * m);  // parent words in, one bit a row out
 }
 
 void nw_fill_y(const uint32_t *ent, const uint32_t *bits, uint8_t *state, uint32_t m,

@@ -139,21 +139,20 @@ __global__ void __launch_bounds__(256) k_sh_counts(ShCountArgs a) {
 
 // k_sh_x_own, counting the own X hits whose winner sits in an earlier slice
 // (a cross-slice link per entry: lk[me * P + owner of the winner])
-__global__ void k_sh_x_own_fast(const uint32_t *xpos, const uint8_t *state, const uint32_t *par,
-                                const uint4 *halo, uint32_t G, uint32_t m, uint32_t poff,
-                                uint32_t *xg, uint8_t *used, Bounds slices, uint32_t me,
-                                uint32_t *lk) {
+__global__ void k_sh_x_own_fast(const uint32_t *par, const uint4 *halo, uint32_t G, uint32_t m,
+                                uint32_t poff, uint32_t *xg, uint8_t *used, Bounds slices,
+                                uint32_t me, uint32_t *lk) {
   __shared__ uint32_t c[MAXP];
   const uint32_t P = slices.P;
   if (threadIdx.x < MAXP) c[threadIdx.x] = 0;
   __syncthreads();
   GRID_STRIDE(k, G + m) {
-    const bool hit = state[xpos[k]] == ST_HIT;
+    const uint32_t w = par[k];
+    const bool hit = w != k;  // (k_sh_x_own)
     if (k < G) {
       used[k] = hit ? 0 : 1;
       continue;
     }
-    const uint32_t w = par[k];
     uint32_t g = NONE;
     if (hit) {
       if (w < G) {
@@ -576,16 +575,16 @@ int classify_sharded_fast(Shard &S, const Geom &geo, const rk_frags_soa *in, con
   uint32_t *xg = R.xg;
   // one rank: entry ids are processing indices, and both axes write their
   // decisions straight into the parent words (as on one device); the X hits
-  // become the Y sort's bitmask (k_nw_x_bits)
+  // become the Y sort's bitmask (k_nw_x_bits, from those parent words)
   solve_x(S, R, hx, G, solo ? xg : nullptr, resolve,
-          [&](const uint32_t *xpos, const uint8_t *state, const uint32_t *par, uint32_t mx) {
+          [&](const uint32_t *par, uint32_t mx) {
             if (solo) {
-              nw_x_bits(xpos, state, m, R.ybits, st);
+              nw_x_bits(par, m, R.ybits, st);
               S.launched("k_nw_x_bits");
             } else {
               kt_begin(st, KID_SH_XOWN);
               k_sh_x_own_fast<<<grid_for(mx, 256, 4096), 256, 0, st>>>(
-                  xpos, state, par, hx, G, m, poff, xg, R.xused, slices, me, gc_lk);
+                  par, hx, G, m, poff, xg, R.xused, slices, me, gc_lk);
               kt_end(st, KID_SH_XOWN, 0.0);
               S.launched("k_sh_x_own_fast");
             }

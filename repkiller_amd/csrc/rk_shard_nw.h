@@ -271,17 +271,21 @@ __global__ void k_lower_bound16(const uint4 *R, uint32_t m, uint64_t v, uint32_t
 }
 
 // own X results -> global winner ids (NONE: X miss); the halo entries' local
-// decisions (1 = in the X list)
-__global__ void k_sh_x_own(const uint32_t *xpos, const uint8_t *state, const uint32_t *par,
-                           const uint4 *halo, uint32_t G, uint32_t m, uint32_t poff,
-                           uint32_t *xg, uint8_t *used) {
+// decisions (1 = in the X list).  The X axis over [halo ; own] runs with
+// Axis::xres == nullptr, so once it is closed every entry of the local CSR,
+// halo entries included, has par[k] = its winner (a hit) or k (in the list):
+// hit = par[k] != k, as in k_nw_x_bits.  (An axis the fast path's queued
+// sweeps left open makes the call repeat; a stale word then gives an arbitrary
+// xg, which is only compared with NONE until k_local_par bounds it.)
+__global__ void k_sh_x_own(const uint32_t *par, const uint4 *halo, uint32_t G, uint32_t m,
+                           uint32_t poff, uint32_t *xg, uint8_t *used) {
   GRID_STRIDE(k, G + m) {
-    const bool hit = state[xpos[k]] == ST_HIT;
+    const uint32_t w = par[k];
+    const bool hit = w != k;
     if (k < G) {
       used[k] = hit ? 0 : 1;
       continue;
     }
-    const uint32_t w = par[k];
     xg[k - G] = !hit ? NONE : w < G ? halo[w].y : poff + (w - G);
   }
 }
@@ -364,7 +368,7 @@ __global__ void k_sh_y_results(const uint3 *yr, const uint8_t *code, const uint3
 enum SlotNw : int {
   SN_HIST = SL_COUNT, SN_SROWS, SN_RIN, SN_RA, SN_RB, SN_YOWN, SN_STAT, SN_YSTAT, SN_SHALO, SN_HX,
   SN_HSEL, SN_SY, SN_YR, SN_YA, SN_YB, SN_XCNT, SN_XOFF, SN_XKEY, SN_XENT, SN_XPK, SN_XNBD,
-  SN_XSTATE, SN_XPOS, SN_EREC, SN_PAR, SN_XGUSED, SN_YKEY, SN_YENT, SN_YPK, SN_YNBD, SN_YST,
+  SN_XSTATE, SN_EREC, SN_PAR, SN_XGUSED, SN_YKEY, SN_YENT, SN_YPK, SN_YNBD, SN_YST,
   SN_XBITS, SN_PARL, SN_SMEM, SN_T0, SN_T1, SN_SGID, SN_MROW, SN_KEY, SN_TAG, SN_GOFF, SN_YSEL,
   SN_SXH, SN_CHIST, SN_COFF, SN_XCNT0, SN_COUNT
 };
@@ -669,9 +673,9 @@ void x_buffers(Shard &S, RecState &R, uint32_t G) {
   S.zero(S.ctrl + SC_WIDE_KEYS, 4);
 }
 // resolve(axis, scratch, 0): the sweeps, with readbacks (resolve_axis) or
-// queued (resolve_axis_queued); own(xpos, state, par, mx): the own results
-// from the resolved axis (k_sh_x_own, k_sh_x_own_fast, or nw_x_bits at one
-// rank).  par: the parent words (null: a buffer of their own).
+// queued (resolve_axis_queued); own(par, mx): the own results from the
+// resolved axis' parent words (k_sh_x_own, k_sh_x_own_fast, or nw_x_bits at
+// one rank).  par: the parent words (null: a buffer of their own).
 template <class Resolve, class Own>
 void solve_x(Shard &S, RecState &R, const uint4 *halo, uint32_t Gc, uint32_t *par,
              Resolve &&resolve, Own &&own) {
@@ -701,10 +705,9 @@ void solve_x(Shard &S, RecState &R, const uint4 *halo, uint32_t Gc, uint32_t *pa
   cx.pk = S.take<uint2>(SN_XPK, mx + 1);
   cx.nbd = S.take<uint8_t>(SN_XNBD, mx + 1);
   cx.state = S.take<uint8_t>(SN_XSTATE, mx + 1);
-  uint32_t *xpos = S.take<uint32_t>(SN_XPOS, mx + 1);
   uint4 *erec = S.take<uint4>(SN_EREC, (size_t)mx * 3 / 4 + 2);
   if (!par) par = S.take<uint32_t>(SN_PAR, mx + 1);
-  nw_x_chunks(R.Ra, mx, nbx, R.max_x, R.maxlen, xoff, cx, xpos, erec, S.ctrl, cc.W, st, halo, Gc);
+  nw_x_chunks(R.Ra, mx, nbx, R.max_x, R.maxlen, xoff, cx, erec, S.ctrl, cc.W, st, halo, Gc);
   S.launched("X chunks");
   Axis ax{cx.key, cx.ent, nullptr, nullptr, cx.state, nullptr, par, cx.pk, cx.nbd,
           S.take<uint32_t>(SL_RLEN, mx), S.take<uint32_t>(SL_RBEG, mx), mx, R.max_x,
@@ -713,7 +716,7 @@ void solve_x(Shard &S, RecState &R, const uint4 *halo, uint32_t Gc, uint32_t *pa
                   S.take<uint8_t>(SL_WPEND, mx / 64 + 1), S.take<uint8_t>(SL_RPEND, mx),
                   S.ctrl + SC_PEND, S.ctrl + SC_SWEEP_COUNT};
   resolve(ax, sc, 0);
-  own(xpos, cx.state, par, mx);
+  own(par, mx);
 }
 
 // ---- Y axis
@@ -947,11 +950,9 @@ int classify_sharded_nw(Shard &S, const Geom &geo, const rk_frags_soa *in, const
   x_buffers(S, R, G);
   uint32_t *xg = R.xg;
   const auto x_own = [&](const uint4 *halo, uint32_t Gc) {
-    return [&, halo, Gc](const uint32_t *xpos, const uint8_t *state, const uint32_t *par,
-                         uint32_t mx) {
+    return [&, halo, Gc](const uint32_t *par, uint32_t mx) {
       kt_begin(st, KID_SH_XOWN);
-      k_sh_x_own<<<grid_for(mx, 256), 256, 0, st>>>(xpos, state, par, halo, Gc, m, R.poff, xg,
-                                                    R.xused);
+      k_sh_x_own<<<grid_for(mx, 256), 256, 0, st>>>(par, halo, Gc, m, R.poff, xg, R.xused);
       kt_end(st, KID_SH_XOWN, 0.0);
       S.launched("k_sh_x_own");
     };

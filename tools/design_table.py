@@ -18,11 +18,11 @@ JOBS = [
     ("k_seg_fine (Y)", "one block per coarse Y-key segment (<= 4096 records in LDS): the 11 fine bits by ballot-ranked LSD rounds, then the Y axis' CSR arrays (key, entry, packed record, neighbour code, state from the carried X-hit bit) written as whole lines", "30"),
     ("k_seg_big", "segments above 4096 records: the same passes through global memory, one block each", "-"),
     ("k_nw_xcount", "(RK_NW_SPLIT=0 only) entries per (strand, X chunk) and owned rows per chunk, over the processing order", "16"),
-    ("k_nw_xchunk", "X axis: a wavefront per chunk places its entries (bin counts, scan, ballot ranks) and writes the owned rows' member records (in-group sort keys)", "50"),
+    ("k_nw_xchunk", "X axis: a wavefront per chunk places its entries (bin counts, scan, ballot ranks) and writes the owned rows' member records (in-group sort keys)", "46"),
     ("k_sweep_fast", "occupancy decisions, first sweep: a wavefront per 64-position window, ballot rounds, 32-bit candidate tests", "26"),
     ("k_sweep_fast_more", "later sweeps: one wavefront per 64 windows handles the still-pending ones", "-"),
     ("k_sweep_long32", "runs of more than 64 entries: a pre-scan for the run's open entries (none: the run is done), then 64 entries at a time against LDS lists (redundant ACTIVE records dropped when a list would overflow)", "-"),
-    ("k_nw_x_bits", "X hits as a bitmask by processing index (ballots over the X states at each fragment's X position), read in order by the first Y pass", "5"),
+    ("k_nw_x_bits", "X hits as a bitmask by processing index, one streaming read of the parent words (bit k = `par[k] != k` after the closed X axis: a hit's parent is its winner, a list entry's itself), read in order by the first Y pass", "4.1"),
     ("k_nw_fill_y", "Y states from the bitmask for later ratio pairs (X hits sit in the Y lists)", "5"),
     ("k_jump", "(RK_ROOTS_FUSED=0 only) chase parent chains to the root, round by round", "16"),
     ("k_nw_assign", "`k_nw_assign_jump`: after the scan that leaves each root's rank in its own parent word (bit 31 set), each member chases its chain (up to 32 links; longer ones listed for `k_nw_assign_rest`) to the first flagged word, whose low bits are its gid, stores that flagged rank back as its parent and feeds the member-sort histograms", "16"),
