@@ -515,6 +515,68 @@ int rk_classify_dbset_to_csv(rk_ctx *ctx, const rk_dbset *dbs, double len_ratio,
  * save in their existing fields, the totals running over all sets;
  * rk_get_batch_stats reports the classification. */
 
+/* ---- selection by repeat flag: the repeat-free set ----------------------
+ *
+ * Every group has exactly one row flagged 0 or 1 (save_frags_from_group,
+ * commonFunctions.cpp:106-115), and the result is in output order
+ * (commonFunctions.cpp:126-128): a stable selection of its entries is the
+ * reference's file with the unwanted Frag lines deleted, and RK_KEEP_UNIQUE
+ * keeps every group id exactly once, in increasing order.  Group ids are not
+ * renumbered: a filtered file's `block` column names the groups of the full
+ * file.  `keep`: bit f set keeps the rows whose flag is f; any other flag value
+ * is never kept.
+ * RK_E_ARG for all of them: keep == 0 or keep > 7, an unknown flag bit, a null
+ * argument where rows are present, an `out` array that is the same pointer as
+ * its `res` array (no in-place selection), RK_RES_DEVICE with a null context, a
+ * decreasing set_off, an n_out[k] larger than its window.  nsets == 0 and
+ * n_out == 0 are RK_OK. */
+enum { RK_KEEP_SINGLETON = 1, RK_KEEP_REPRESENTATIVE = 2, RK_KEEP_REPEATED = 4,
+       RK_KEEP_UNIQUE = 3 /* the repeat-free set: one row per group */, RK_KEEP_ALL = 7 };
+
+/* The rows of res whose flag (commonFunctions.cpp:106-115) is in `keep`, in
+ * res's order (commonFunctions.cpp:126-128).  out: caller-allocated,
+ * res->n_out entries per array.  The first out->n_out (set by the call) are
+ * filled.  Entries from there on are NOT written.  out->n_groups =
+ * res->n_groups.  flags: 0 (host arrays; ctx may be NULL and no device is
+ * touched) or RK_RES_DEVICE (device arrays on ctx's device). */
+int rk_result_select(rk_ctx *ctx, const rk_result *res, uint32_t keep, uint32_t flags,
+                     rk_result *out);
+/* The same per set of an rk_batch_result (flags of commonFunctions.cpp:106-115,
+ * order of :126-128, per set): set k's kept rows go to set_off[k] on.
+ * set_off[0] may be above zero, as for rk_classify_batch: entries before it
+ * belong to no set and are neither read nor written.
+ * res->n_out is read (HOST, nsets).  out->n_out (HOST, nsets) is set.
+ * out->n_groups is copied from res->n_groups when both are non-null. */
+int rk_batch_result_select(rk_ctx *ctx, uint32_t nsets, const uint64_t *set_off,
+                           const rk_batch_result *res, uint32_t keep, uint32_t flags,
+                           rk_batch_result *out);
+/* The last selection on a context (flags: commonFunctions.cpp:106-115; rows in
+ * the order of :126-128): rows read, used slots by flag, rows kept, sets, and
+ * the HIP-event time of the device passes (0 for a host selection). */
+typedef struct { uint64_t rows_in, by_flag[4] /* 0, 1, 2, other, over used slots */, kept;
+                 uint32_t sets; double device_ms; } rk_select_stats;
+int rk_get_select_stats(const rk_ctx *ctx, rk_select_stats *st);
+/* Slots of a tile of the device selection. */
+uint32_t rk_select_tile(void);
+
+/* rk_classify_db_pairs_to_csv / rk_classify_dbset_to_csv with the selection
+ * (flags of commonFunctions.cpp:106-115, order of :126-128) between the
+ * classification and the save.  The result arrays still never leave the device.
+ * n_out / n_groups report the classification.  n_kept (nullable HOST array)
+ * reports the rows written.  The header is the echoed header, unchanged (its
+ * `Total fragments` line is an echo of the input); the body is the lines of
+ * the full file whose last field is a kept flag, in the full file's order.
+ * With RK_KEEP_ALL no selection runs: rk_classify_db_pairs_to_csv and
+ * rk_classify_dbset_to_csv are these with RK_KEEP_ALL.  rk_egress_stats.rows
+ * is the rows written. */
+int rk_classify_db_pairs_to_csv_keep(rk_ctx *ctx, const rk_db *db, const double *len_ratio,
+                                     const double *pos_ratio, uint32_t npairs,
+                                     const char *const *paths, uint32_t keep, uint64_t *n_out,
+                                     uint64_t *n_groups, uint64_t *n_kept);
+int rk_classify_dbset_to_csv_keep(rk_ctx *ctx, const rk_dbset *dbs, double len_ratio,
+                                  double pos_ratio, const char *const *paths, uint32_t keep,
+                                  uint64_t *n_out, uint64_t *n_groups, uint64_t *n_kept);
+
 /* ---- synthetic inputs --------------------------------- */
 
 typedef struct {

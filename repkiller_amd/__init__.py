@@ -62,12 +62,18 @@ EXPORTS = (
     "rk_db_write_csv_device", "rk_classify_db_pairs_to_csv", "rk_get_egress_stats",
     "rk_dbset_load_csv_device", "rk_dbset_free", "rk_dbset_view", "rk_classify_dbset",
     "rk_dbset_write_csv_device", "rk_classify_dbset_to_csv", "rk_dbset_write_csv",
+    "rk_result_select", "rk_batch_result_select", "rk_get_select_stats",
+    "rk_classify_db_pairs_to_csv_keep", "rk_classify_dbset_to_csv_keep",
 )
 # declared too, returning uint32_t (sizes the device CSV parser was built with)
-EXPORTS_U32 = ("rk_csv_max_line", "rk_csv_tile")
+EXPORTS_U32 = ("rk_csv_max_line", "rk_csv_tile", "rk_select_tile")
 RK_DB_KEEP_DEVICE = 1
 RK_DB_KEEP_ROWS = 3  # all nine columns resident: the device egress formats from them
 RK_RES_DEVICE = 1    # rk_db_write_csv_device: the result arrays are device pointers
+# selection by repeat flag (RK_KEEP_*): bit f keeps the rows whose flag is f
+KEEP_SINGLETON, KEEP_REPRESENTATIVE, KEEP_REPEATED = 1, 2, 4
+KEEP_UNIQUE = 3  # the repeat-free set: one row per group
+KEEP_ALL = 7
 
 
 class RkError(RuntimeError):
@@ -141,6 +147,12 @@ class EgressStats(ctypes.Structure):
                 ("upload_ms", ctypes.c_double), ("device_ms", ctypes.c_double),
                 ("host_fix_ms", ctypes.c_double), ("d2h_write_ms", ctypes.c_double),
                 ("total_ms", ctypes.c_double)]
+
+
+class SelectStats(ctypes.Structure):
+    _fields_ = [("rows_in", ctypes.c_uint64), ("by_flag", ctypes.c_uint64 * 4),
+                ("kept", ctypes.c_uint64), ("sets", ctypes.c_uint32),
+                ("device_ms", ctypes.c_double)]
 
 
 ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
@@ -300,6 +312,21 @@ def load_library() -> ctypes.CDLL:
         "rk_classify_dbset_to_csv": (ctypes.c_int, [vp, vp, ctypes.c_double, ctypes.c_double,
                                                     ctypes.POINTER(ctypes.c_char_p), _u64p,
                                                     _u64p]),
+        "rk_result_select": (ctypes.c_int, [vp, ctypes.POINTER(Result), ctypes.c_uint32,
+                                            ctypes.c_uint32, ctypes.POINTER(Result)]),
+        "rk_batch_result_select": (ctypes.c_int, [vp, ctypes.c_uint32, vp,
+                                                  ctypes.POINTER(BatchResult), ctypes.c_uint32,
+                                                  ctypes.c_uint32, ctypes.POINTER(BatchResult)]),
+        "rk_get_select_stats": (ctypes.c_int, [vp, ctypes.POINTER(SelectStats)]),
+        "rk_classify_db_pairs_to_csv_keep": (ctypes.c_int, [vp, vp, ctypes.POINTER(ctypes.c_double),
+                                                            ctypes.POINTER(ctypes.c_double),
+                                                            ctypes.c_uint32,
+                                                            ctypes.POINTER(ctypes.c_char_p),
+                                                            ctypes.c_uint32, _u64p, _u64p, _u64p]),
+        "rk_classify_dbset_to_csv_keep": (ctypes.c_int, [vp, vp, ctypes.c_double, ctypes.c_double,
+                                                         ctypes.POINTER(ctypes.c_char_p),
+                                                         ctypes.c_uint32, _u64p, _u64p, _u64p]),
+        "rk_select_tile": (ctypes.c_uint32, []),
         "rk_csv_max_line": (ctypes.c_uint32, []),
         "rk_csv_tile": (ctypes.c_uint32, []),
     }
@@ -372,6 +399,27 @@ class ClassifyResult:
     def as_struct(self) -> Result:
         return Result(_ptr(self.out_order), _ptr(self.gid), _ptr(self.repval),
                       int(self.out_order.shape[0]), self.n_groups)
+
+
+def select(res: ClassifyResult, keep: int) -> ClassifyResult:
+    """The rows of `res` whose repeat flag is in `keep` (KEEP_*), in res's order
+    (rk_result_select on the host: no device is touched).  Group ids are not
+    renumbered; KEEP_UNIQUE keeps one row per group."""
+    n = int(res.out_order.shape[0])
+    src = ClassifyResult(np.ascontiguousarray(res.gid, np.uint32),
+                         np.ascontiguousarray(res.repval, np.uint8),
+                         np.ascontiguousarray(res.out_order, np.uint32), res.n_groups)
+    gid, rep, order = np.empty(n, np.uint32), np.empty(n, np.uint8), np.empty(n, np.uint32)
+    r, out = src.as_struct(), Result(_ptr(order), _ptr(gid), _ptr(rep), 0, 0)
+    _check(load_library().rk_result_select(None, ctypes.byref(r), keep, 0, ctypes.byref(out)),
+           "rk_result_select")
+    k = int(out.n_out)
+    return ClassifyResult(gid[:k].copy(), rep[:k].copy(), order[:k].copy(), int(out.n_groups))
+
+
+def select_tile() -> int:
+    """Slots of a tile of the device selection (rk_select_tile)."""
+    return int(load_library().rk_select_tile())
 
 
 class FragmentsDatabase:
@@ -750,11 +798,14 @@ class Context:
         k = res.n_out
         return ClassifyResult(gid[:k].copy(), rep[:k].copy(), order[:k].copy(), int(res.n_groups))
 
-    def classify_db_to_csv(self, db: "FragmentsDatabase", pairs, paths) -> list:
+    def classify_db_to_csv(self, db: "FragmentsDatabase", pairs, paths,
+                           keep: int = KEEP_ALL, with_kept: bool = False) -> list:
         """Classify a keep_rows=True database at every (len_ratio, pos_ratio) of
         `pairs` and write pair i to paths[i] from the device: the result arrays
-        never come to the host (rk_classify_db_pairs_to_csv).  Returns
-        [(n_out, n_groups)] per pair."""
+        never come to the host (rk_classify_db_pairs_to_csv_keep).  keep: the
+        repeat flags whose rows are written (KEEP_*).  Returns [(n_out, n_groups)]
+        per pair, or with with_kept=True [(n_out, n_groups, n_kept)], n_kept the
+        rows written."""
         pairs, paths = list(pairs), list(paths)
         q = len(pairs)
         if q != len(paths):
@@ -763,13 +814,16 @@ class Context:
         pr = (ctypes.c_double * max(q, 1))(*[p[1] for p in pairs])
         ps = (ctypes.c_char_p * max(q, 1))(*[p.encode() for p in paths])
         n_out, n_groups = np.zeros(max(q, 1), np.uint64), np.zeros(max(q, 1), np.uint64)
-        rc = load_library().rk_classify_db_pairs_to_csv(
-            self._h, db._h, lr, pr, q, ps, n_out.ctypes.data_as(_u64p),
-            n_groups.ctypes.data_as(_u64p))
+        n_kept = np.zeros(max(q, 1), np.uint64)
+        rc = load_library().rk_classify_db_pairs_to_csv_keep(
+            self._h, db._h, lr, pr, q, ps, keep, n_out.ctypes.data_as(_u64p),
+            n_groups.ctypes.data_as(_u64p), n_kept.ctypes.data_as(_u64p))
         if rc == -2:
             raise RkError(rc, "Could not open an output path of " + ", ".join(paths))
         if rc != RK_OK:
             raise RkError(rc, self.last_error())
+        if with_kept:
+            return [(int(n_out[i]), int(n_groups[i]), int(n_kept[i])) for i in range(q)]
         return [(int(n_out[i]), int(n_groups[i])) for i in range(q)]
 
     def classify_dbset(self, dbs: "FragmentsDatabaseSet", len_ratio: float = 0.3,
@@ -795,22 +849,71 @@ class Context:
         return out
 
     def classify_dbset_to_csv(self, dbs: "FragmentsDatabaseSet", paths, len_ratio: float = 0.3,
-                              pos_ratio: float = 0.3) -> tuple:
+                              pos_ratio: float = 0.3, keep: int = KEEP_ALL,
+                              with_kept: bool = False) -> tuple:
         """Classify a keep_rows=True FragmentsDatabaseSet and write set k to
-        paths[k] from the device (rk_classify_dbset_to_csv): the result arrays
-        never come to the host.  Returns (n_out, n_groups) as uint64 arrays."""
+        paths[k] from the device (rk_classify_dbset_to_csv_keep): the result arrays
+        never come to the host.  keep: the repeat flags whose rows are written
+        (KEEP_*).  Returns (n_out, n_groups) as uint64 arrays, or with
+        with_kept=True (n_out, n_groups, n_kept), n_kept the rows written per set."""
         paths = [str(p) for p in paths]
         ns = dbs.nsets
         if len(paths) != ns:
             raise ValueError("classify_dbset_to_csv: one path per set")
         arr = (ctypes.c_char_p * max(ns, 1))(*[p.encode() for p in paths])
         n_out, n_groups = np.zeros(max(ns, 1), np.uint64), np.zeros(max(ns, 1), np.uint64)
-        rc = load_library().rk_classify_dbset_to_csv(
-            self._h, dbs._h, len_ratio, pos_ratio, arr, n_out.ctypes.data_as(_u64p),
-            n_groups.ctypes.data_as(_u64p))
+        kept = np.zeros(max(ns, 1), np.uint64)
+        rc = load_library().rk_classify_dbset_to_csv_keep(
+            self._h, dbs._h, len_ratio, pos_ratio, arr, keep, n_out.ctypes.data_as(_u64p),
+            n_groups.ctypes.data_as(_u64p), kept.ctypes.data_as(_u64p))
         if rc != RK_OK:
             raise RkError(rc, self.last_error())
+        if with_kept:
+            return n_out[:ns], n_groups[:ns], kept[:ns]
         return n_out[:ns], n_groups[:ns]
+
+    def select_device(self, out_order, gid, repval, n_out: int, keep: int, out_order_out,
+                      gid_out, repval_out) -> int:
+        """The device selection of one result (rk_result_select, RK_RES_DEVICE):
+        device tensors in, the kept rows into the first entries of the three
+        output tensors (n_out entries each; the rest is not written).  Returns
+        the kept count."""
+        r = Result(out_order.data_ptr(), gid.data_ptr(), repval.data_ptr(), int(n_out), 0)
+        o = Result(out_order_out.data_ptr(), gid_out.data_ptr(), repval_out.data_ptr(), 0, 0)
+        rc = load_library().rk_result_select(self._h, ctypes.byref(r), keep, RK_RES_DEVICE,
+                                             ctypes.byref(o))
+        if rc != RK_OK:
+            raise RkError(rc, self.last_error())
+        return int(o.n_out)
+
+    def select_batch(self, set_off, n_out, out_order, gid, repval, keep: int, out_order_out,
+                     gid_out, repval_out) -> np.ndarray:
+        """The selection per set of a result in rk_batch_result layout
+        (rk_batch_result_select): numpy arrays (selected on the host) or device
+        tensors.  Set k's kept rows go to set_off[k] on in the output arrays;
+        returns the kept counts per set (uint64)."""
+        off = np.ascontiguousarray(set_off, np.uint64)
+        ns = off.shape[0] - 1
+        no = np.ascontiguousarray(n_out, np.uint64)
+        kept = np.zeros(max(ns, 1), np.uint64)
+        arrs = (out_order, gid, repval, out_order_out, gid_out, repval_out)
+        dev = not isinstance(out_order, np.ndarray)
+        p = [a.data_ptr() if dev else _ptr(a) for a in arrs]
+        res = BatchResult(p[0], p[1], p[2], _ptr(no), 0)
+        out = BatchResult(p[3], p[4], p[5], kept.ctypes.data, 0)
+        rc = load_library().rk_batch_result_select(self._h, ns, off.ctypes.data, ctypes.byref(res),
+                                                   keep, RK_RES_DEVICE if dev else 0,
+                                                   ctypes.byref(out))
+        if rc != RK_OK:
+            raise RkError(rc, self.last_error())
+        return kept[:ns]
+
+    def select_stats(self) -> dict:
+        """The last selection on this context (rk_get_select_stats)."""
+        s = SelectStats()
+        _check(load_library().rk_get_select_stats(self._h, ctypes.byref(s)))
+        return {"rows_in": s.rows_in, "by_flag": [int(v) for v in s.by_flag], "kept": s.kept,
+                "sets": s.sets, "device_ms": s.device_ms}
 
     def egress_stats(self) -> dict:
         """The last device CSV save on this context (rk_get_egress_stats)."""

@@ -1178,6 +1178,7 @@ extern "C" void rk_destroy(rk_ctx *ctx) {
   rk::batch_destroy(ctx);
   if (ctx->ws) (void)hipFree(ctx->ws);
   if (ctx->io) (void)hipFree(ctx->io);
+  if (ctx->sel) (void)hipFree(ctx->sel);
   for (void *p : ctx->txt)
     if (p) (void)hipFree(p);
   if (ctx->ws_wide) (void)hipFree(ctx->ws_wide);

@@ -43,6 +43,15 @@
 // outputs are formatted on the GPU too and every set's text goes to its own
 // file (rk_classify_dbset_to_csv).  --timing prints the ingress, batch and
 // egress stats as one JSON line on stderr.
+//
+// --keep all|unique|repeated|groups|<1..7> (every route that writes a CSV):
+// only the rows whose repeat flag is in the mask are written (bit 0 singletons,
+// bit 1 representatives, bit 2 repeated rows; unique = 3 is the repeat-free
+// set, one row per group; groups = 6; all = 7, the default).  The header is
+// echoed unchanged and group ids are not renumbered.  The host routes select
+// on the host between the classification and the writer (rk_result_select);
+// --device-save selects on the GPU (the *_to_csv_keep entry points).  --timing
+// then adds the select stats.
 #include <atomic>
 #include <chrono>
 #include <fstream>
@@ -59,9 +68,9 @@
 static void print_help() {
   std::printf("Repkiller (MI355X) v0.9.b-compatible\n");
   std::printf("Usage: ./rk_repkiller [--device N] [--gpus P [--same-device] [--comm rccl|local]] "
-              "[--timing] [--save-soa cache.soa | --soa | --device-parse [--device-save]] <input_file_path> <output_file_path> "
+              "[--timing] [--keep all|unique|repeated|groups|<1..7>] [--save-soa cache.soa | --soa | --device-parse [--device-save]] <input_file_path> <output_file_path> "
               "<length_ratio> <position_ratio> [<length_ratio> <position_ratio>]...\n");
-  std::printf("       ./rk_repkiller [--device N] --batch <list of input<TAB>output lines> "
+  std::printf("       ./rk_repkiller [--device N] [--keep MASK] --batch <list of input<TAB>output lines> "
               "[--device-parse [--device-save] [--timing]] <length_ratio> <position_ratio>\n");
   std::fflush(stdout);
 }
@@ -69,6 +78,57 @@ static void print_help() {
 static double now_s() {
   using namespace std::chrono;
   return duration<double>(steady_clock::now().time_since_epoch()).count();
+}
+
+static bool parse_keep(const char *s, uint32_t *keep) {
+  if (!std::strcmp(s, "all")) return *keep = RK_KEEP_ALL, true;
+  if (!std::strcmp(s, "unique")) return *keep = RK_KEEP_UNIQUE, true;
+  if (!std::strcmp(s, "repeated")) return *keep = RK_KEEP_REPEATED, true;
+  if (!std::strcmp(s, "groups")) return *keep = RK_KEEP_REPRESENTATIVE | RK_KEEP_REPEATED, true;
+  char *end = nullptr;
+  const unsigned long v = std::strtoul(s, &end, 10);
+  if (end == s || *end || v < 1 || v > RK_KEEP_ALL || s[0] < '0' || s[0] > '9') return false;
+  *keep = (uint32_t)v;
+  return true;
+}
+
+// the select stats of a run: summed over its selections
+struct SelectTotals {
+  rk_select_stats st{};
+  // a host selection of `in` (host arrays) that kept `kept` rows: the rows by
+  // flag are counted here, with or without a context
+  void add(const rk_result &in, uint64_t kept) {
+    st.rows_in += in.n_out, st.kept += kept, st.sets += 1;
+    for (uint64_t k = 0; k < in.n_out; ++k) ++st.by_flag[in.repval[k] < 3 ? in.repval[k] : 3];
+  }
+  void from(const rk_ctx *ctx) { rk_get_select_stats(ctx, &st); }
+  void print(const char *open, const char *close) const {
+    std::fprintf(stderr,
+                 "%s\"select\": {\"rows_in\": %llu, \"by_flag\": [%llu, %llu, %llu, %llu], "
+                 "\"kept\": %llu, \"sets\": %u, \"device_ms\": %.3f}%s",
+                 open, (unsigned long long)st.rows_in, (unsigned long long)st.by_flag[0],
+                 (unsigned long long)st.by_flag[1], (unsigned long long)st.by_flag[2],
+                 (unsigned long long)st.by_flag[3], (unsigned long long)st.kept, st.sets,
+                 st.device_ms, close);
+  }
+};
+
+// the host selection of one result: *r becomes the kept rows, held in `own`,
+// which must outlive it (keep all: r is left as it is)
+struct Selected {
+  std::vector<uint32_t> order, gid;
+  std::vector<uint8_t> rep;
+};
+static int select_host_result(rk_ctx *ctx, uint32_t keep, rk_result *r, Selected *own,
+                              SelectTotals *tot) {
+  if (keep == RK_KEEP_ALL) return RK_OK;
+  own->order.resize(r->n_out), own->gid.resize(r->n_out), own->rep.resize(r->n_out);
+  rk_result out{own->order.data(), own->gid.data(), own->rep.data(), 0, 0};
+  const int rc = rk_result_select(ctx, r, keep, 0, &out);
+  if (rc) return rc;
+  tot->add(*r, out.n_out);
+  *r = out;
+  return RK_OK;
 }
 
 static bool parse_ratio(const char *s, double *v) {
@@ -162,7 +222,7 @@ static bool read_batch_list(const char *list_path, std::vector<std::string> &ins
 // one combined resident database, classified from there; the outputs written by
 // the host per file, or formatted on the GPU too
 static int run_batch_device(const char *list_path, double lr, double pr, int device,
-                            bool device_save, bool timing) {
+                            bool device_save, bool timing, uint32_t keep) {
   std::vector<std::string> ins, outs;
   if (!read_batch_list(list_path, ins, outs)) return 1;
   const size_t ns = ins.size();
@@ -196,17 +256,31 @@ static int run_batch_device(const char *list_path, double lr, double pr, int dev
   rk_dbset_view(dbs, &nsets, &off, nullptr, nullptr, nullptr, nullptr, nullptr);
   const uint64_t n = off[nsets];
   std::vector<uint64_t> n_out(ns + 1), n_groups(ns + 1);
+  SelectTotals sel;
   double t2;
   if (device_save) {
-    rc = rk_classify_dbset_to_csv(ctx, dbs, lr, pr, op.data(), n_out.data(), n_groups.data());
+    rc = rk_classify_dbset_to_csv_keep(ctx, dbs, lr, pr, op.data(), keep, n_out.data(),
+                                       n_groups.data(), nullptr);
     t2 = now_s();
     if (rc) return fail("classification or device save");
+    if (keep != RK_KEEP_ALL) sel.from(ctx);
   } else {
     std::vector<uint32_t> gid(n), order(n);
     std::vector<uint8_t> rep(n);
     rk_batch_result br{order.data(), gid.data(), rep.data(), n_out.data(), n_groups.data()};
     rc = rk_classify_dbset(ctx, dbs, lr, pr, &br);
     if (rc) return fail("classification");
+    std::vector<uint32_t> sgid, sorder;
+    std::vector<uint8_t> srep;
+    std::vector<uint64_t> kept(ns + 1);
+    if (keep != RK_KEEP_ALL) {
+      sgid.resize(n), sorder.resize(n), srep.resize(n);
+      rk_batch_result sb{sorder.data(), sgid.data(), srep.data(), kept.data(), nullptr};
+      rc = rk_batch_result_select(ctx, nsets, off, &br, keep, 0, &sb);
+      if (rc) return fail("selection");
+      sel.from(ctx);
+      order.swap(sorder), gid.swap(sgid), rep.swap(srep), n_out.swap(kept);
+    }
     for (size_t k = 0; k < ns && !rc; ++k) {
       const rk_result r{order.data() + off[k], gid.data() + off[k], rep.data() + off[k], n_out[k],
                         n_groups[k]};
@@ -232,7 +306,7 @@ static int run_batch_device(const char *list_path, double lr, double pr, int dev
                  "\"device_ms\": %.3f}, "
                  "\"egress\": {\"rows\": %llu, \"bytes\": %llu, \"host_rows\": %llu, "
                  "\"chunks\": %u, \"upload_ms\": %.3f, \"device_ms\": %.3f, "
-                 "\"host_fix_ms\": %.3f, \"d2h_write_ms\": %.3f, \"total_ms\": %.3f}}\n",
+                 "\"host_fix_ms\": %.3f, \"d2h_write_ms\": %.3f, \"total_ms\": %.3f}",
                  ns, (unsigned long long)n, t1 - t0, t2 - t1, (unsigned long long)ing.body_bytes,
                  (unsigned long long)ing.lines, (unsigned long long)ing.accepted,
                  (unsigned long long)ing.host_lines, ing.windows, ing.h2d_ms, ing.device_ms,
@@ -240,6 +314,8 @@ static int run_batch_device(const char *list_path, double lr, double pr, int dev
                  bs.batched_sets, bs.device_ms, (unsigned long long)eg.rows,
                  (unsigned long long)eg.bytes, (unsigned long long)eg.host_rows, eg.chunks,
                  eg.upload_ms, eg.device_ms, eg.host_fix_ms, eg.d2h_write_ms, eg.total_ms);
+    if (keep != RK_KEEP_ALL) sel.print(", ", "}\n");
+    else std::fprintf(stderr, "}\n");
   }
   rk_dbset_free(dbs);
   rk_destroy(ctx);
@@ -248,7 +324,7 @@ static int run_batch_device(const char *list_path, double lr, double pr, int dev
 }
 
 // --batch: every listed CSV through one batched classification
-static int run_batch(const char *list_path, double lr, double pr, int device) {
+static int run_batch(const char *list_path, double lr, double pr, int device, uint32_t keep) {
   std::vector<std::string> ins, outs;
   if (!read_batch_list(list_path, ins, outs)) return 1;
   const size_t ns = ins.size();
@@ -313,9 +389,15 @@ static int run_batch(const char *list_path, double lr, double pr, int device) {
     return 1;
   }
   rk_destroy(ctx);
+  SelectTotals sel;
   for (size_t k = 0; k < ns && !rc; ++k) {
-    const rk_result r{order.data() + off[k], gid.data() + off[k], rep.data() + off[k], n_out[k],
-                      n_groups[k]};
+    rk_result r{order.data() + off[k], gid.data() + off[k], rep.data() + off[k], n_out[k],
+                n_groups[k]};
+    Selected own;
+    if ((rc = select_host_result(nullptr, keep, &r, &own, &sel))) {
+      std::fprintf(stderr, "selection failed (%d)\n", rc);
+      break;
+    }
     if ((rc = rk_db_write_csv(dbs[k], outs[k].c_str(), &r)))
       std::fprintf(stderr, "writing %s failed (%d)\n", outs[k].c_str(), rc);
   }
@@ -330,6 +412,8 @@ int main(int argc, char **argv) {
   bool timing = false, same_device = false, soa_in = false, device_parse = false;
   bool device_save = false;
   const char *comm_kind = nullptr, *save_soa = nullptr, *batch_list = nullptr;
+  const char *keep_arg = nullptr;
+  uint32_t keep = RK_KEEP_ALL;
   std::vector<const char *> pos;
   for (int i = 1; i < argc; ++i) {
     if (!std::strcmp(argv[i], "--device") && i + 1 < argc) device = std::atoi(argv[++i]);
@@ -342,7 +426,13 @@ int main(int argc, char **argv) {
     else if (!std::strcmp(argv[i], "--device-save")) device_save = true;
     else if (!std::strcmp(argv[i], "--save-soa") && i + 1 < argc) save_soa = argv[++i];
     else if (!std::strcmp(argv[i], "--batch") && i + 1 < argc) batch_list = argv[++i];
+    else if (!std::strcmp(argv[i], "--keep") && i + 1 < argc) keep_arg = argv[++i];
     else pos.push_back(argv[i]);
+  }
+  if (keep_arg && !parse_keep(keep_arg, &keep)) {
+    std::fprintf(stderr, "Invalid --keep value %s.\n", keep_arg);
+    print_help();
+    return 1;
   }
   if (gpus < 1 || gpus > 32 ||
       (comm_kind && std::strcmp(comm_kind, "rccl") && std::strcmp(comm_kind, "local"))) {
@@ -368,8 +458,9 @@ int main(int argc, char **argv) {
       print_help();
       return 1;
     }
-    if (device_parse) return run_batch_device(batch_list, lr, pr, device, device_save, timing);
-    return run_batch(batch_list, lr, pr, device);
+    if (device_parse)
+      return run_batch_device(batch_list, lr, pr, device, device_save, timing, keep);
+    return run_batch(batch_list, lr, pr, device, keep);
   }
   const bool local = comm_kind ? !std::strcmp(comm_kind, "local") : same_device;
   // init_args (commonFunctions.cpp:14-29)
@@ -467,21 +558,23 @@ int main(int argc, char **argv) {
     std::vector<const char *> paths(q, out_path.c_str());
     for (size_t i = 0; i < q; ++i) lrs[i] = params[i].first, prs[i] = params[i].second;
     const double a = now_s();
-    rc = rk_classify_db_pairs_to_csv(ctx, db, lrs.data(), prs.data(), (uint32_t)q, paths.data(),
-                                     nullptr, nullptr);
+    rc = rk_classify_db_pairs_to_csv_keep(ctx, db, lrs.data(), prs.data(), (uint32_t)q,
+                                          paths.data(), keep, nullptr, nullptr, nullptr);
     if (rc == RK_E_IO) {
       // the saver thread's rule, pair by pair (SaverQueue.cpp:16-20)
       size_t fallback_count = 0;
       rc = RK_OK;
       for (size_t i = 0; i < q && !rc; ++i) {
         const char *one = out_path.c_str();
-        rc = rk_classify_db_pairs_to_csv(ctx, db, &lrs[i], &prs[i], 1, &one, nullptr, nullptr);
+        rc = rk_classify_db_pairs_to_csv_keep(ctx, db, &lrs[i], &prs[i], 1, &one, keep, nullptr,
+                                              nullptr, nullptr);
         if (rc != RK_E_IO) continue;
         const std::string alt = "represults-" + std::to_string(++fallback_count) + ".csv";
         std::fprintf(stderr, "Couldn't access %s, saving into %s\n", out_path.c_str(),
                      alt.c_str());
         one = alt.c_str();
-        rc = rk_classify_db_pairs_to_csv(ctx, db, &lrs[i], &prs[i], 1, &one, nullptr, nullptr);
+        rc = rk_classify_db_pairs_to_csv_keep(ctx, db, &lrs[i], &prs[i], 1, &one, keep, nullptr,
+                                              nullptr, nullptr);
       }
     }
     const double t_all = now_s() - a;
@@ -498,7 +591,10 @@ int main(int argc, char **argv) {
     rk_get_ingress_stats(ctx, &ing);
     rk_egress_stats eg{};
     rk_get_egress_stats(ctx, &eg);
+    SelectTotals sel;
+    sel.from(ctx);  // the last pair's, as the egress stats
     rk_destroy(ctx);
+    if (timing && keep != RK_KEEP_ALL) sel.print("{", "}\n");
     if (timing) {
       std::fprintf(stderr,
                    "{\"ingress\": {\"body_bytes\": %llu, \"lines\": %llu, \"accepted\": %llu, "
@@ -562,7 +658,22 @@ int main(int argc, char **argv) {
   rk_stats stt{};
   if (ctx) rk_get_stats(ctx, &stt);
   const double dev_ms = stt.device_ms;
-  for (size_t i = 0; i < q; ++i) rk_saver_add(sq, out_path.c_str(), &rs[i], soa.n);
+  // the selection of every pair's result on the host, then the saver thread as
+  // it is (its fall-back file included)
+  SelectTotals sel;
+  for (size_t i = 0; i < q && !rc; ++i) {
+    Selected own;
+    rk_result r = rs[i];
+    if ((rc = select_host_result(ctx, keep, &r, &own, &sel))) break;
+    rk_saver_add(sq, out_path.c_str(), &r, soa.n);
+  }
+  if (rc) {
+    std::fprintf(stderr, "selection failed (%d)\n", rc);
+    rk_saver_stop(sq);
+    rk_destroy(ctx);
+    rk_db_free(db);
+    return 1;
+  }
   double t2 = now_s();
   rc = rk_saver_stop(sq);
   double t3 = now_s();
@@ -577,6 +688,7 @@ int main(int argc, char **argv) {
                  (unsigned long long)ing.body_bytes, (unsigned long long)ing.lines,
                  (unsigned long long)ing.accepted, (unsigned long long)ing.host_lines, ing.windows,
                  ing.h2d_ms, ing.device_ms, ing.host_fix_ms, ing.d2h_ms, ing.total_ms);
+  if (timing && keep != RK_KEEP_ALL) sel.print("{", "}\n");
   if (timing)
     std::fprintf(stderr,
                  "{\"frags\": %llu, \"pairs\": %zu, \"load_s\": %.6f, \"classify_s\": %.6f, "

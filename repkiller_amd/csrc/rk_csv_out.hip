@@ -934,6 +934,23 @@ int check_set_args(rk_ctx *ctx, const rk_dbset *dbs, bool rows, const char *what
   return RK_OK;
 }
 
+// The selection by repeat flag between a classification and its save
+// (rk_select.hip): the kept rows of device arrays in rk_batch_result layout go to
+// ctx->sel in the same layout, kept[k] rows for set k.
+int selected(rk_ctx *ctx, uint32_t ns, const uint64_t *off, const uint64_t *n_out, Res in,
+             uint32_t keep, Res *out, uint64_t *kept) {
+  const size_t n = ns ? off[ns] : 0;
+  rk::Carve pc{nullptr};
+  pc.take<uint32_t>(n), pc.take<uint32_t>(n), pc.take<uint8_t>(n);
+  int rc = rk::grow(ctx, &ctx->sel, &ctx->sel_cap, pc.off, "selected result");
+  if (rc) return rc;
+  rk::Carve c{(char *)ctx->sel};
+  uint32_t *so = c.take<uint32_t>(n), *sg = c.take<uint32_t>(n);
+  uint8_t *sr = c.take<uint8_t>(n);
+  *out = Res{so, sg, sr};
+  return rk::select_device(ctx, ns, off, n_out, in.order, in.gid, in.rep, keep, so, sg, sr, kept);
+}
+
 template <class F>
 int guarded(rk_ctx *ctx, const char *what, F &&body) {
   try {
@@ -992,10 +1009,11 @@ extern "C" int rk_dbset_write_csv_device(rk_ctx *ctx, const rk_dbset *dbs,
                  [&] { return write_set_device(ctx, dbs, paths, res, flags); });
 }
 
-extern "C" int rk_classify_dbset_to_csv(rk_ctx *ctx, const rk_dbset *dbs, double len_ratio,
-                                        double pos_ratio, const char *const *paths,
-                                        uint64_t *n_out, uint64_t *n_groups) {
-  if (!ctx || !dbs) return RK_E_ARG;
+extern "C" int rk_classify_dbset_to_csv_keep(rk_ctx *ctx, const rk_dbset *dbs, double len_ratio,
+                                             double pos_ratio, const char *const *paths,
+                                             uint32_t keep, uint64_t *n_out, uint64_t *n_groups,
+                                             uint64_t *n_kept) {
+  if (!ctx || !dbs || keep == 0 || keep > (uint32_t)RK_KEEP_ALL) return RK_E_ARG;
   const uint32_t ns = (uint32_t)dbs->header.size();
   if (ns && !paths) return RK_E_ARG;
   for (uint32_t k = 0; k < ns; ++k)
@@ -1005,7 +1023,7 @@ extern "C" int rk_classify_dbset_to_csv(rk_ctx *ctx, const rk_dbset *dbs, double
   if (rc) return rc;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   return guarded(ctx, "rk_classify_dbset_to_csv", [&]() -> int {
-    std::vector<uint64_t> no(ns), ng(ns);
+    std::vector<uint64_t> no(ns), ng(ns), nk(ns);
     rk_batch_result dres{nullptr, nullptr, nullptr, no.data(), ng.data()};
     int rc2 = dbset_classify_resident(ctx, dbs, len_ratio, pos_ratio, &dres);
     if (rc2) return rc2;
@@ -1013,8 +1031,28 @@ extern "C" int rk_classify_dbset_to_csv(rk_ctx *ctx, const rk_dbset *dbs, double
       if (n_out) n_out[k] = no[k];
       if (n_groups) n_groups[k] = ng[k];
     }
+    if (keep != (uint32_t)RK_KEEP_ALL) {
+      // the kept rows of every set, at the set's own offset (the layout the save reads)
+      Res sel;
+      if ((rc2 = selected(ctx, ns, dbs->set_off.data(), no.data(),
+                          Res{dres.out_order, dres.gid, dres.repval}, keep, &sel, nk.data())))
+        return rc2;
+      dres = rk_batch_result{const_cast<uint32_t *>(sel.order), const_cast<uint32_t *>(sel.gid),
+                             const_cast<uint8_t *>(sel.rep), nk.data(), ng.data()};
+    } else {
+      nk = no;
+    }
+    for (uint32_t k = 0; k < ns; ++k)
+      if (n_kept) n_kept[k] = nk[k];
     return write_set_device(ctx, dbs, paths, &dres, RK_RES_DEVICE);
   });
+}
+
+extern "C" int rk_classify_dbset_to_csv(rk_ctx *ctx, const rk_dbset *dbs, double len_ratio,
+                                        double pos_ratio, const char *const *paths,
+                                        uint64_t *n_out, uint64_t *n_groups) {
+  return rk_classify_dbset_to_csv_keep(ctx, dbs, len_ratio, pos_ratio, paths, RK_KEEP_ALL, n_out,
+                                       n_groups, nullptr);
 }
 
 extern "C" int rk_db_write_csv_device(rk_ctx *ctx, const rk_db *db, const char *path,
@@ -1038,11 +1076,14 @@ extern "C" int rk_db_write_csv_device(rk_ctx *ctx, const rk_db *db, const char *
   }
 }
 
-extern "C" int rk_classify_db_pairs_to_csv(rk_ctx *ctx, const rk_db *db, const double *len_ratio,
-                                           const double *pos_ratio, uint32_t npairs,
-                                           const char *const *paths, uint64_t *n_out,
-                                           uint64_t *n_groups) {
-  if (!ctx || !db || !len_ratio || !pos_ratio || !paths || npairs == 0) return RK_E_ARG;
+extern "C" int rk_classify_db_pairs_to_csv_keep(rk_ctx *ctx, const rk_db *db,
+                                                const double *len_ratio, const double *pos_ratio,
+                                                uint32_t npairs, const char *const *paths,
+                                                uint32_t keep, uint64_t *n_out,
+                                                uint64_t *n_groups, uint64_t *n_kept) {
+  if (!ctx || !db || !len_ratio || !pos_ratio || !paths || npairs == 0 || keep == 0 ||
+      keep > (uint32_t)RK_KEEP_ALL)
+    return RK_E_ARG;
   for (uint32_t q = 0; q < npairs; ++q)
     if (!paths[q]) return RK_E_ARG;
   ctx->err.clear();
@@ -1056,8 +1097,21 @@ extern "C" int rk_classify_db_pairs_to_csv(rk_ctx *ctx, const rk_db *db, const d
       if (n_out) n_out[q] = dres[q].n_out;
       if (n_groups) n_groups[q] = dres[q].n_groups;
     }
-    for (uint32_t q = 0; q < npairs; ++q)
-      if ((rc = write_device(ctx, db, paths[q], &dres[q], RK_RES_DEVICE))) return rc;
+    for (uint32_t q = 0; q < npairs; ++q) {
+      rk_result r = dres[q];
+      if (keep != (uint32_t)RK_KEEP_ALL) {
+        const uint64_t off[2] = {0, r.n_out};
+        Res sel;
+        uint64_t kept = 0;
+        if ((rc = selected(ctx, 1, off, &r.n_out, Res{r.out_order, r.gid, r.repval}, keep, &sel,
+                           &kept)))
+          return rc;
+        r = rk_result{const_cast<uint32_t *>(sel.order), const_cast<uint32_t *>(sel.gid),
+                      const_cast<uint8_t *>(sel.rep), kept, r.n_groups};
+      }
+      if (n_kept) n_kept[q] = r.n_out;
+      if ((rc = write_device(ctx, db, paths[q], &r, RK_RES_DEVICE))) return rc;
+    }
     return RK_OK;
   } catch (const std::bad_alloc &) {
     (void)hipStreamSynchronize(ctx->stream);
@@ -1068,6 +1122,14 @@ extern "C" int rk_classify_db_pairs_to_csv(rk_ctx *ctx, const rk_db *db, const d
     ctx->err = "unexpected C++ exception";
     return RK_E_INTERNAL;
   }
+}
+
+extern "C" int rk_classify_db_pairs_to_csv(rk_ctx *ctx, const rk_db *db, const double *len_ratio,
+                                           const double *pos_ratio, uint32_t npairs,
+                                           const char *const *paths, uint64_t *n_out,
+                                           uint64_t *n_groups) {
+  return rk_classify_db_pairs_to_csv_keep(ctx, db, len_ratio, pos_ratio, npairs, paths,
+                                          RK_KEEP_ALL, n_out, n_groups, nullptr);
 }
 
 extern "C" int rk_get_egress_stats(const rk_ctx *ctx, rk_egress_stats *st) {

@@ -65,6 +65,9 @@ struct rk_ctx {
   rk_egress_stats egress{};    // the last rk_db_write_csv_device (rk_csv_out.hip)
   void *txt[2] = {};           // its two chunk text buffers, grow-only
   size_t txt_cap[2] = {};
+  rk_select_stats select{};    // the last rk_*_select (rk_select.hip)
+  void *sel = nullptr;         // the selected result of the *_to_csv_keep routes, grow-only
+  size_t sel_cap = 0;
   // the sharded driver's fast path (rk_shard_fast.h): its all-gather messages
   // (pinned, every rank's), the stage fingerprints of the last call that
   // completed on it (a stage whose gathered counts match needs no agreement
@@ -96,6 +99,14 @@ namespace rk {
 // rk_csv.hip: the body of rk_classify_db_pairs up to the download
 int db_classify_resident(rk_ctx *ctx, const rk_db *db, const double *len_ratio,
                          const double *pos_ratio, uint32_t npairs, std::vector<rk_result> &dres);
+
+// rk_select.hip: the stable selection by repeat flag of device arrays in
+// rk_batch_result layout (set k owns slots [off[k], off[k] + n_out[k]), off and
+// n_out HOST arrays); kept[k] (HOST) = rows of set k written to `out` from
+// off[k] on.  Returns with the stream idle.
+int select_device(rk_ctx *ctx, uint32_t nsets, const uint64_t *off, const uint64_t *n_out,
+                  const uint32_t *order, const uint32_t *gid, const uint8_t *rep, uint32_t keep,
+                  uint32_t *out_order, uint32_t *out_gid, uint8_t *out_rep, uint64_t *kept);
 
 #define HIPCHK(ctx, call)                                                          \
   do {                                                                             \
