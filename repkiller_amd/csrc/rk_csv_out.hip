@@ -25,13 +25,14 @@
 // (rk::io_d2h_sink).  Scratch comes from ctx->ws; uploaded result arrays from
 // ctx->io.
 //
-// A batch of sets (rk_dbset_write_csv_device) runs the same chunks over the
-// slots of an rk_batch_result: k_outb_len takes the place of the length pass
-// (it finds each slot's set, turns a used slot into its combined row, gives an
-// unused one length 0), the other passes run unchanged on the combined rows, and
-// k_outb_cuts gives the text offset at which every set of the chunk starts.
-// The writers split each pinned slot at those cuts and pwrite every piece into
-// its own set's file (SetFiles).
+// One driver (write_chunks) runs this loop for both routes.  FileRoute: the
+// n_out output rows, pwritten behind the header of one file.  SetRoute, a batch
+// of sets (rk_dbset_write_csv_device): the slots of an rk_batch_result.
+// k_outb_len takes the place of the length pass (it finds each slot's set, turns
+// a used slot into its combined row, gives an unused one length 0), the other
+// passes run unchanged on the combined rows, and k_outb_cuts gives the text
+// offset at which every set of the chunk starts.  The writers split each pinned
+// slot at those cuts and pwrite every piece into its own set's file (SetFiles).
 #include <fcntl.h>
 #include <unistd.h>
 
@@ -66,9 +67,12 @@ struct OCols {
   const uint8_t *strand;
 };
 
+// a result's arrays: device memory in the kernels, which only read them; not
+// const, since carve_result's callers fill them; host memory only as the source
+// of upload_result
 struct Res {
-  const uint32_t *order, *gid;
-  const uint8_t *rep;
+  uint32_t *order, *gid;
+  uint8_t *rep;
 };
 
 // counters of a chunk
@@ -85,23 +89,24 @@ __device__ inline rk::OutRow gather(const OCols &c, uint32_t i) {
   return r;
 }
 
-// rows [0, cnt) of the chunk (r is the chunk's slice of the result arrays)
-__global__ __launch_bounds__(OB) void k_out_len(OCols c, uint64_t n, Res r, uint32_t cnt,
-                                               uint8_t *len8, uint8_t *hst, uint32_t *blk_tot,
-                                               Ctr *ctr) {
-  __shared__ uint32_t lds[OB];
-  const uint32_t k = blockIdx.x * OB + threadIdx.x;
+// The two length kernels share their body.  row_len: the text length of input
+// row i as output row k of the chunk's slice r; a ROW_HOST row has length 0 until
+// the fix-up patches it.
+__device__ __forceinline__ uint32_t row_len(const OCols &c, uint32_t i, const Res &r, uint32_t k,
+                                            bool *host) {
+  const rk::OutRow row = gather(c, i);
   uint32_t len = 0;
-  bool host = false;
+  *host = rk::csv_row(row, r.gid[k], r.rep[k], nullptr, &len) == rk::ROW_HOST;
+  return *host ? 0 : len;
+}
+
+// len_tail: row k's length byte and ROW_HOST flag, the block's byte total, and
+// the block's share of the chunk's counters (every thread of the block calls it)
+__device__ __forceinline__ void len_tail(uint32_t k, uint32_t cnt, uint32_t len, bool host,
+                                         uint8_t *len8, uint8_t *hst, uint32_t *blk_tot,
+                                         Ctr *ctr) {
+  __shared__ uint32_t lds[OB];
   if (k < cnt) {
-    const uint32_t i = r.order[k];
-    if (i >= n) {
-      atomicOr(&ctr->err, OERR_ORDER);
-    } else {
-      const rk::OutRow row = gather(c, i);
-      host = rk::csv_row(row, r.gid[k], r.rep[k], nullptr, &len) == rk::ROW_HOST;
-      if (host) len = 0;
-    }
     len8[k] = (uint8_t)len;
     hst[k] = host ? 1 : 0;
   }
@@ -113,6 +118,21 @@ __global__ __launch_bounds__(OB) void k_out_len(OCols c, uint64_t n, Res r, uint
     if (total) atomicAdd(&ctr->bytes, (unsigned long long)total);
     if (nh) atomicAdd(&ctr->host_rows, (unsigned long long)nh);
   }
+}
+
+// rows [0, cnt) of the chunk (r is the chunk's slice of the result arrays)
+__global__ __launch_bounds__(OB) void k_out_len(OCols c, uint64_t n, Res r, uint32_t cnt,
+                                               uint8_t *len8, uint8_t *hst, uint32_t *blk_tot,
+                                               Ctr *ctr) {
+  const uint32_t k = blockIdx.x * OB + threadIdx.x;
+  uint32_t len = 0;
+  bool host = false;
+  if (k < cnt) {
+    const uint32_t i = r.order[k];
+    if (i >= n) atomicOr(&ctr->err, OERR_ORDER);
+    else len = row_len(c, i, r, k, &host);
+  }
+  len_tail(k, cnt, len, host, len8, hst, blk_tot, ctr);
 }
 
 // ---- a batch of sets (rk_dbset_write_csv_device): the result is in
@@ -147,7 +167,6 @@ __device__ inline uint32_t set_of(const SetTab &s, uint32_t lo, uint64_t p) {
 __global__ __launch_bounds__(OB) void k_outb_len(OCols c, SetTab s, Res r, uint64_t k0,
                                                 uint32_t cnt, uint32_t *crow, uint8_t *len8,
                                                 uint8_t *hst, uint32_t *blk_tot, Ctr *ctr) {
-  __shared__ uint32_t lds[OB];
   const uint32_t k = blockIdx.x * OB + threadIdx.x;
   uint32_t len = 0;
   bool host = false;
@@ -163,23 +182,12 @@ __global__ __launch_bounds__(OB) void k_outb_len(OCols c, SetTab s, Res r, uint6
         atomicOr(&ctr->err, OERR_ORDER);
       } else {
         i = (uint32_t)(base + o);
-        const rk::OutRow row = gather(c, i);
-        host = rk::csv_row(row, r.gid[k], r.rep[k], nullptr, &len) == rk::ROW_HOST;
-        if (host) len = 0;
+        len = row_len(c, i, r, k, &host);
       }
     }
     crow[k] = i;
-    len8[k] = (uint8_t)len;
-    hst[k] = host ? 1 : 0;
   }
-  uint32_t total;
-  (void)rk::block_excl_scan<OB>(len, lds, &total);
-  const int nh = __syncthreads_count(host);
-  if (threadIdx.x == 0) {
-    blk_tot[blockIdx.x] = total;
-    if (total) atomicAdd(&ctr->bytes, (unsigned long long)total);
-    if (nh) atomicAdd(&ctr->host_rows, (unsigned long long)nh);
-  }
+  len_tail(k, cnt, len, host, len8, hst, blk_tot, ctr);
 }
 
 // cuts[j] = chunk-local text offset of the first slot of set ks + j, for the m
@@ -337,34 +345,20 @@ struct Save {
   uint32_t *poff, *blk_tot, *blk_off;
   Ctr *ctr;
   uint32_t *perr;  // the put passes' error bits: cleared once, read once at the end
-  // a batch of sets (null / unused on the single route): the device tables, the
-  // host's set_off, the chunk's combined rows, and per text buffer the cuts
-  const uint64_t *hoff = nullptr;
-  SetTab tab{};
-  uint32_t *crow = nullptr, *cuts[2] = {};
-  uint32_t *hcuts[2] = {};  // pinned
 
-  void carve(rk::Carve &c, uint32_t R, uint32_t nsets = 0) {
+  void carve(rk::Carve &c, uint32_t R) {
     const uint32_t nb = (R + OB - 1) / OB;
     len8 = c.take<uint8_t>(R), hst = c.take<uint8_t>(R), poff = c.take<uint32_t>(R);
     blk_tot = c.take<uint32_t>(nb), blk_off = c.take<uint32_t>(nb + 1);
     ctr = c.take<Ctr>(1), perr = c.take<uint32_t>(1);
-    if (!nsets) return;
-    crow = c.take<uint32_t>(R);
-    cuts[0] = c.take<uint32_t>(nsets), cuts[1] = c.take<uint32_t>(nsets);
-    tab.off = c.take<uint64_t>((size_t)nsets + 1), tab.n_out = c.take<uint64_t>(nsets);
-    tab.ns = nsets;
   }
-  // the chunk's slice of the result as the passes after the length pass read it
-  Res chunk_res(uint64_t k0) const {
-    return Res{hoff ? crow : res.order + k0, res.gid + k0, res.rep + k0};
-  }
+  // the result entries of the chunk that starts at k0
+  Res slice(uint64_t k0) const { return Res{res.order + k0, res.gid + k0, res.rep + k0}; }
 
-  // host rows of chunk [k0, k0 + cnt): list, format, upload, patch the lengths
-  int fix_up(uint64_t k0, uint32_t cnt, uint32_t nhost, int par, uint64_t *added) {
+  // host rows of the chunk's cnt rows r: list, format, upload, patch the lengths
+  int fix_up(const Res &r, uint32_t cnt, uint32_t nhost, int par, uint64_t *added) {
     hipStream_t s = ctx->stream;
     const uint32_t nb = (cnt + OB - 1) / OB;
-    const Res r = chunk_res(k0);
     Patch &p = patch[par];
     p.release();
     void *list = nullptr;
@@ -446,19 +440,17 @@ struct Save {
     return RK_OK;
   }
 
-  // passes 1-4 of chunk c = rows [k0, k0 + cnt); returns with the put pass queued
-  int format_chunk(uint64_t c, uint64_t k0, uint32_t cnt, Chunk *out) {
+  // passes 1-4 of chunk c = rows [k0, k0 + cnt); returns with the put pass queued.
+  // The route launches its length pass and names the rows the other passes read;
+  // after the scan it may queue work of its own (a batch: the sets' cuts).
+  template <class Route>
+  int format_chunk(Route &rt, uint64_t c, uint64_t k0, uint32_t cnt, Chunk *out) {
     hipStream_t s = ctx->stream;
     const int par = (int)(c & 1);
     const uint32_t nb = (cnt + OB - 1) / OB;
-    const Res r = chunk_res(k0);
     HIPCHK(ctx, hipEventRecord(ev.e[0], s));
     HIPCHK(ctx, hipMemsetAsync(ctr, 0, sizeof(Ctr), s));
-    if (hoff)
-      k_outb_len<<<nb, OB, 0, s>>>(cols, tab, Res{res.order + k0, res.gid + k0, res.rep + k0}, k0,
-                                   cnt, crow, len8, hst, blk_tot, ctr);
-    else
-      k_out_len<<<nb, OB, 0, s>>>(cols, n, r, cnt, len8, hst, blk_tot, ctr);
+    const Res r = rt.len_pass(*this, k0, cnt, nb);
     HIPCHK(ctx, hipMemcpyAsync(ctx->host, ctr, sizeof(Ctr), hipMemcpyDeviceToHost, s));
     HIPCHK(ctx, hipEventRecord(ev.e[1], s));
     HIPCHK(ctx, hipEventSynchronize(ev.e[1]));
@@ -477,7 +469,7 @@ struct Save {
     if (got.host_rows) {
       const double t = rk::wall_ms();
       uint64_t added = 0;
-      const int rc = fix_up(k0, cnt, (uint32_t)got.host_rows, par, &added);
+      const int rc = fix_up(r, cnt, (uint32_t)got.host_rows, par, &added);
       if (rc) return rc;
       bytes += added;
       st->host_rows += got.host_rows;
@@ -488,21 +480,7 @@ struct Save {
     if (rc) return rc;
     HIPCHK(ctx, hipEventRecord(ev.e[2 + 2 * par], s));
     rk::k_csv_scan<uint32_t><<<1, 1024, 0, s>>>(blk_tot, nb, blk_off);
-    if (hoff) {
-      // the sets whose first slot lies in the chunk; the last chunk also takes
-      // the empty sets at the very end
-      const uint64_t *b = hoff, *e = hoff + tab.ns;
-      out->ks = (uint32_t)(std::lower_bound(b, e, k0) - b);
-      out->m = (k0 + cnt >= hoff[tab.ns] ? tab.ns
-                                         : (uint32_t)(std::lower_bound(b, e, k0 + cnt) - b)) -
-               out->ks;
-      if (out->m) {
-        k_outb_cuts<<<(out->m + OB - 1) / OB, OB, 0, s>>>(tab.off, out->ks, out->m, k0, cnt, len8,
-                                                          blk_off, cuts[par]);
-        HIPCHK(ctx, hipMemcpyAsync(hcuts[par], cuts[par], (size_t)out->m * 4,
-                                   hipMemcpyDeviceToHost, s));
-      }
-    }
+    if ((rc = rt.after_scan(*this, par, k0, cnt, out))) return rc;
     k_out_put<<<nb, OB, 0, s>>>(cols, r, cnt, len8, hst, poff, (const char *)patch[par].text,
                                 blk_off, (char *)ctx->txt[par], bytes, perr);
     HIPCHK(ctx, hipEventRecord(ev.e[3 + 2 * par], s));
@@ -513,97 +491,111 @@ struct Save {
   }
 };
 
-int write_device(rk_ctx *ctx, const rk_db *db, const char *path, const rk_result *res,
+// n entries of a result (u32 order, u32 gid, u8 rep) in one of the context's
+// grow-only buffers
+int carve_result(rk_ctx *ctx, void **buf, size_t *cap, size_t n, const char *what, Res *out) {
+  rk::Carve pc{nullptr};
+  pc.take<uint32_t>(n), pc.take<uint32_t>(n), pc.take<uint8_t>(n);
+  const int rc = rk::grow(ctx, buf, cap, pc.off, what);
+  if (rc) return rc;
+  rk::Carve c{(char *)*buf};
+  out->order = c.take<uint32_t>(n), out->gid = c.take<uint32_t>(n), out->rep = c.take<uint8_t>(n);
+  return RK_OK;
+}
+
+// the n entries of a host result uploaded to ctx->io
+int upload_result(rk_ctx *ctx, const Res &host, size_t n, Res *dev) {
+  const double t = rk::wall_ms();
+  int rc = carve_result(ctx, &ctx->io, &ctx->io_cap, n, "result upload", dev);
+  if (rc) return rc;
+  if ((rc = rk::io_h2d(ctx, {{host.order, dev->order, n * 4},
+                             {host.gid, dev->gid, n * 4},
+                             {host.rep, dev->rep, n}})))
+    return rc;
+  ctx->egress.upload_ms = rk::wall_ms() - t;
+  return RK_OK;
+}
+
+// The chunk driver of both routes.  in: the result's `entries` entries, device
+// arrays with RK_RES_DEVICE, host arrays otherwise.  The route (FileRoute,
+// SetRoute) has: open, the checks and files before any device work (*work: there
+// is text to format); total, the rows or slots the chunks are cut over; set_up,
+// its own state behind the driver's in ctx->ws, called twice as a Carve is
+// (sizes first; then pointers, pinned memory and uploads); len_pass and
+// after_scan (format_chunk); begin_chunk, sink, end_chunk around a chunk's way
+// down; stop, a file failed; done, after the last chunk alone, which finish
+// cannot tell from a failure; finish, the call's code.
+template <class Route>
+int write_chunks(rk_ctx *ctx, const rk_db *db, Route &rt, const Res &in, uint64_t entries,
                  uint32_t flags) {
   const double t0 = rk::wall_ms();
   rk_egress_stats &st = ctx->egress;
   st = rk_egress_stats{};
-  // the file first, as the host route: an open failure does nothing else
-  FdCloser f{::open(path, O_WRONLY | O_CREAT | O_TRUNC, 0644)};
-  if (f.fd < 0) return RK_E_IO;
-  const uint64_t n = db->x_start.size(), n_out = res->n_out;
-  if (n_out > 0xFFFFFFFFull || (n_out && n == 0)) return RK_E_ARG;
-  bool ok = pwrite_all(f.fd, db->header.data(), db->header.size(), 0);
-  uint64_t file_off = db->header.size();
-  auto finish = [&](int rc) {
-    const int fd = f.fd;
-    f.fd = -1;
-    if (::close(fd) != 0) ok = false;
+  bool work = false;
+  int rc = rt.open(ctx, &work);
+  if (rc) return rc;
+  auto finish = [&](int code) {
+    code = rt.finish(ctx, code);
     st.total_ms = rk::wall_ms() - t0;
-    return rc ? rc : ok ? RK_OK : RK_E_IO;
+    return code;
   };
-  if (!n_out || !ok) return finish(RK_OK);
+  if (!work) return finish(RK_OK);
 
   HIPCHK(ctx, hipSetDevice(ctx->device));
   Save S{ctx, db};
   S.cols = OCols{db->dev_x,     db->dev_y,     db->dev_xe,  db->dev_ye,    db->dev_len,
                  db->dev_score, db->dev_ident, db->dev_sim, db->dev_strand};
-  S.n = n;
+  S.n = db->x_start.size();
   S.st = &st;
   for (auto &e : S.ev.e) HIPCHK(ctx, hipEventCreate(&e));
-  int rc;
-  if (flags & RK_RES_DEVICE) {
-    S.res = Res{res->out_order, res->gid, res->repval};
-  } else {
-    const double t = rk::wall_ms();
-    rk::Carve pc{nullptr};
-    pc.take<uint32_t>(n_out), pc.take<uint32_t>(n_out), pc.take<uint8_t>(n_out);
-    if ((rc = rk::grow(ctx, &ctx->io, &ctx->io_cap, pc.off, "result upload"))) return rc;
-    rk::Carve c{(char *)ctx->io};
-    uint32_t *dord = c.take<uint32_t>(n_out), *dgid = c.take<uint32_t>(n_out);
-    uint8_t *drep = c.take<uint8_t>(n_out);
-    if ((rc = rk::io_h2d(ctx, {{res->out_order, dord, (size_t)n_out * 4},
-                               {res->gid, dgid, (size_t)n_out * 4},
-                               {res->repval, drep, (size_t)n_out}})))
-      return rc;
-    S.res = Res{dord, dgid, drep};
-    st.upload_ms = rk::wall_ms() - t;
-  }
-  const uint32_t R = (uint32_t)std::min<uint64_t>(chunk_rows(), n_out);
+  S.res = in;
+  if (!(flags & RK_RES_DEVICE) && (rc = upload_result(ctx, in, entries, &S.res))) return rc;
+  const uint64_t total = rt.total;
+  const uint32_t R = (uint32_t)std::min<uint64_t>(chunk_rows(), total);
   rk::Carve ps{nullptr};
-  S.carve(ps, R);
+  S.carve(ps, R), (void)rt.set_up(ctx, ps, R);
   if ((rc = rk::grow(ctx, &ctx->ws, &ctx->ws_cap, ps.off, "csv rows out"))) return rc;
   rk::Carve cs{(char *)ctx->ws};
   S.carve(cs, R);
+  if ((rc = rt.set_up(ctx, cs, R))) return rc;
 
-  const uint64_t nchunks = (n_out + R - 1) / R;
-  auto rows_of = [&](uint64_t c) { return (uint32_t)std::min<uint64_t>(R, n_out - c * R); };
   hipStream_t s = ctx->stream;
+  HIPCHK(ctx, hipMemsetAsync(S.perr, 0, 4, s));
+  const uint64_t nchunks = (total + R - 1) / R;
+  auto rows_of = [&](uint64_t c) { return (uint32_t)std::min<uint64_t>(R, total - c * R); };
   // on any failure below the stream is drained before the patch buffers go
   auto fail = [&](int code) {
     (void)hipStreamSynchronize(s);
     return finish(code);
   };
-  HIPCHK(ctx, hipMemsetAsync(S.perr, 0, 4, s));
   Chunk cur, next;
-  if ((rc = S.format_chunk(0, 0, rows_of(0), &cur))) return fail(rc);
+  if ((rc = S.format_chunk(rt, 0, 0, rows_of(0), &cur))) return fail(rc);
   for (uint64_t c = 0; c < nchunks; ++c) {
     const int par = (int)(c & 1);
     // chunk c + 1 is formatted (the other text buffer) before chunk c's
     // download starts to wait: its put pass runs beside the copies and writes
-    if (c + 1 < nchunks && (rc = S.format_chunk(c + 1, (c + 1) * R, rows_of(c + 1), &next)))
+    if (c + 1 < nchunks &&
+        (rc = S.format_chunk(rt, c + 1, (c + 1) * R, rows_of(c + 1), &next)))
       return fail(rc);
     const double t = rk::wall_ms();
-    const uint64_t at = file_off;
-    rc = rk::io_d2h_sink(ctx, ctx->txt[par], (size_t)cur.bytes, S.ev.e[3 + 2 * par],
-                         [&](const char *p, size_t len, size_t off) {
-                           return pwrite_all(f.fd, p, len, at + off);
-                         });
+    hipEvent_t put = S.ev.e[3 + 2 * par];
+    if ((rc = rt.begin_chunk(ctx, c * R, cur, par, put))) return fail(rc);
+    rc = rk::io_d2h_sink(ctx, ctx->txt[par], (size_t)cur.bytes, put,
+                         [&](const char *p, size_t len, size_t o) { return rt.sink(p, len, o); });
+    rt.end_chunk(cur, rc, &st);
     st.d2h_write_ms += rk::wall_ms() - t;
-    if (rc == 1) ok = false, rc = RK_OK;
-    if (rc) return fail(rc);
+    if (rc != 1 && rc) return fail(rc);  // (1: a sink call failed; the route knows)
     // the put pass of chunk c is complete (the copy stream waited for it)
     float ms = 0;
-    HIPCHK(ctx, hipEventElapsedTime(&ms, S.ev.e[2 + 2 * par], S.ev.e[3 + 2 * par]));
+    HIPCHK(ctx, hipEventElapsedTime(&ms, S.ev.e[2 + 2 * par], put));
     st.device_ms += ms;
     S.patch[par].release();
-    file_off += cur.bytes;
-    st.rows += cur.cnt;
     st.bytes += cur.bytes;
     ++st.chunks;
     cur = next;
-    if (!ok) return fail(RK_OK);
+    if (rt.stop()) return fail(RK_OK);
   }
+  rt.done(&st);
   HIPCHK(ctx, hipMemcpyAsync(ctx->host, S.perr, 4, hipMemcpyDeviceToHost, s));
   HIPCHK(ctx, hipStreamSynchronize(s));
   if (*ctx->host) {  // (the put pass' own error word, not a control block's)
@@ -611,6 +603,56 @@ int write_device(rk_ctx *ctx, const rk_db *db, const char *path, const rk_result
     return finish(RK_E_INTERNAL);
   }
   return finish(RK_OK);
+}
+
+// One file: the rows' text follows the header.
+struct FileRoute {
+  const rk_db *db;
+  const char *path;
+  uint64_t total;  // n_out
+  FdCloser f{-1};
+  uint64_t at = 0;  // the file offset of the chunk's text
+  bool ok = true;
+
+  int open(rk_ctx *, bool *work) {
+    // the file first, as the host route: an open failure does nothing else
+    f.fd = ::open(path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
+    if (f.fd < 0) return RK_E_IO;
+    if (total > 0xFFFFFFFFull || (total && db->x_start.empty())) return RK_E_ARG;
+    ok = pwrite_all(f.fd, db->header.data(), db->header.size(), 0);
+    at = db->header.size();
+    *work = total && ok;
+    return RK_OK;
+  }
+  int set_up(rk_ctx *, rk::Carve &, uint32_t) { return RK_OK; }
+  Res len_pass(Save &S, uint64_t k0, uint32_t cnt, uint32_t nb) {
+    const Res r = S.slice(k0);
+    k_out_len<<<nb, OB, 0, S.ctx->stream>>>(S.cols, S.n, r, cnt, S.len8, S.hst, S.blk_tot, S.ctr);
+    return r;
+  }
+  int after_scan(Save &, int, uint64_t, uint32_t, Chunk *) { return RK_OK; }
+  int begin_chunk(rk_ctx *, uint64_t, const Chunk &, int, hipEvent_t) { return RK_OK; }
+  bool sink(const char *p, size_t len, size_t off) { return pwrite_all(f.fd, p, len, at + off); }
+  void end_chunk(const Chunk &c, int rc, rk_egress_stats *st) {
+    if (rc == 1) ok = false;  // a pwrite failed
+    else if (rc) return;
+    at += c.bytes;
+    st->rows += c.cnt;
+  }
+  bool stop() const { return !ok; }
+  void done(rk_egress_stats *) {}
+  int finish(rk_ctx *, int rc) {
+    const int fd = f.fd;
+    f.fd = -1;
+    if (::close(fd) != 0) ok = false;
+    return rc ? rc : ok ? RK_OK : RK_E_IO;
+  }
+};
+
+int write_device(rk_ctx *ctx, const rk_db *db, const char *path, const rk_result *res,
+                 uint32_t flags) {
+  FileRoute rt{db, path, res->n_out};
+  return write_chunks(ctx, db, rt, Res{res->out_order, res->gid, res->repval}, res->n_out, flags);
 }
 
 int check_args(rk_ctx *ctx, const rk_db *db, const char *what) {
@@ -772,124 +814,99 @@ int set_io_error(rk_ctx *ctx, const SetFiles &f) {
   return RK_E_IO;
 }
 
-int write_set_device(rk_ctx *ctx, const rk_dbset *dbs, const char *const *paths,
-                     const rk_batch_result *res, uint32_t flags) {
-  const double t0 = rk::wall_ms();
-  rk_egress_stats &st = ctx->egress;
-  st = rk_egress_stats{};
-  const rk_db *db = dbs->db;
-  const uint32_t ns = (uint32_t)dbs->header.size();
-  const uint64_t *off = dbs->set_off.data();
-  const uint64_t n = off[ns];  // rows = slots
-  uint64_t rows = 0;
-  for (uint32_t k = 0; k < ns; ++k) {
-    if (res->n_out[k] > off[k + 1] - off[k]) {
-      ctx->err = "set " + std::to_string(k) + ": n_out exceeds the set's rows";
-      return RK_E_ARG;
-    }
-    rows += res->n_out[k];
-  }
-  SetFiles files{dbs, paths};
-  auto finish = [&](int rc) -> int {
-    st.total_ms = rk::wall_ms() - t0;
-    if (rc) return rc;
-    if (files.bad != ~0u || files.io_bad) return set_io_error(ctx, files);
-    return RK_OK;
-  };
-  if (!rows) {  // no text at all: every file is its header
-    for (uint32_t k = 0; k < ns && files.bad == ~0u; ++k) files.header_only(k);
-    return finish(RK_OK);
-  }
-
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  Save S{ctx, db};
-  S.cols = OCols{db->dev_x,     db->dev_y,     db->dev_xe,  db->dev_ye,    db->dev_len,
-                 db->dev_score, db->dev_ident, db->dev_sim, db->dev_strand};
-  S.n = n;
-  S.st = &st;
-  S.hoff = off;
-  for (auto &e : S.ev.e) HIPCHK(ctx, hipEventCreate(&e));
+// A batch of sets: the chunks run over the slots of an rk_batch_result, and
+// every chunk's text is split at the sets' cuts into their files.
+struct SetRoute {
+  const rk_dbset *dbs;
+  const rk_batch_result *res;
+  SetFiles files;
+  uint32_t ns;
+  const uint64_t *off;  // the host's set_off
+  uint64_t total;       // off[ns]: slots = rows
+  uint64_t rows = 0;    // the sum of n_out
+  // device: the set tables, the chunk's combined rows, per text buffer the cuts
+  SetTab tab{};
+  uint32_t *crow = nullptr, *cuts[2] = {};
   PinnedFree pin;
-  HIPCHK(ctx, hipHostMalloc(&pin.p, (size_t)ns * 8, hipHostMallocDefault));
-  S.hcuts[0] = (uint32_t *)pin.p, S.hcuts[1] = S.hcuts[0] + ns;
-  int rc;
-  if (flags & RK_RES_DEVICE) {
-    S.res = Res{res->out_order, res->gid, res->repval};
-  } else {
-    const double t = rk::wall_ms();
-    rk::Carve pc{nullptr};
-    pc.take<uint32_t>(n), pc.take<uint32_t>(n), pc.take<uint8_t>(n);
-    if ((rc = rk::grow(ctx, &ctx->io, &ctx->io_cap, pc.off, "result upload"))) return rc;
-    rk::Carve c{(char *)ctx->io};
-    uint32_t *dord = c.take<uint32_t>(n), *dgid = c.take<uint32_t>(n);
-    uint8_t *drep = c.take<uint8_t>(n);
-    if ((rc = rk::io_h2d(ctx, {{res->out_order, dord, (size_t)n * 4},
-                               {res->gid, dgid, (size_t)n * 4},
-                               {res->repval, drep, (size_t)n}})))
-      return rc;
-    S.res = Res{dord, dgid, drep};
-    st.upload_ms = rk::wall_ms() - t;
+  uint32_t *hcuts[2] = {};  // pinned
+
+  SetRoute(const rk_dbset *d, const char *const *paths, const rk_batch_result *r)
+      : dbs(d), res(r), files{d, paths}, ns((uint32_t)d->header.size()),
+        off(d->set_off.data()), total(off[ns]) {}
+
+  int open(rk_ctx *ctx, bool *work) {
+    for (uint32_t k = 0; k < ns; ++k) {
+      if (res->n_out[k] > off[k + 1] - off[k]) {
+        ctx->err = "set " + std::to_string(k) + ": n_out exceeds the set's rows";
+        return RK_E_ARG;
+      }
+      rows += res->n_out[k];
+    }
+    if (!rows)  // no text at all: every file is its header
+      for (uint32_t k = 0; k < ns && files.bad == ~0u; ++k) files.header_only(k);
+    *work = rows != 0;
+    return RK_OK;
   }
-  const uint32_t R = (uint32_t)std::min<uint64_t>(chunk_rows(), n);
-  rk::Carve ps{nullptr};
-  S.carve(ps, R, ns);
-  if ((rc = rk::grow(ctx, &ctx->ws, &ctx->ws_cap, ps.off, "csv rows out"))) return rc;
-  rk::Carve cs{(char *)ctx->ws};
-  S.carve(cs, R, ns);
-
-  hipStream_t s = ctx->stream;
-  HIPCHK(ctx, hipMemcpyAsync((void *)S.tab.off, off, ((size_t)ns + 1) * 8, hipMemcpyHostToDevice, s));
-  HIPCHK(ctx, hipMemcpyAsync((void *)S.tab.n_out, res->n_out, (size_t)ns * 8,
-                             hipMemcpyHostToDevice, s));
-  HIPCHK(ctx, hipMemsetAsync(S.perr, 0, 4, s));
-  HIPCHK(ctx, hipStreamSynchronize(s));  // (the tables are pageable host memory)
-
-  const uint64_t nchunks = (n + R - 1) / R;
-  auto rows_of = [&](uint64_t c) { return (uint32_t)std::min<uint64_t>(R, n - c * R); };
-  // on any failure below the stream is drained before the patch buffers go
-  auto fail = [&](int code) {
-    (void)hipStreamSynchronize(s);
-    return finish(code);
-  };
-  Chunk cur, next;
-  if ((rc = S.format_chunk(0, 0, rows_of(0), &cur))) return fail(rc);
-  for (uint64_t c = 0; c < nchunks; ++c) {
-    const int par = (int)(c & 1);
-    if (c + 1 < nchunks && (rc = S.format_chunk(c + 1, (c + 1) * R, rows_of(c + 1), &next)))
-      return fail(rc);
-    const double t = rk::wall_ms();
+  int set_up(rk_ctx *ctx, rk::Carve &c, uint32_t R) {
+    crow = c.take<uint32_t>(R);
+    cuts[0] = c.take<uint32_t>(ns), cuts[1] = c.take<uint32_t>(ns);
+    tab.off = c.take<uint64_t>((size_t)ns + 1), tab.n_out = c.take<uint64_t>(ns);
+    tab.ns = ns;
+    if (!c.base) return RK_OK;  // the sizing pass ends here
+    // placed: the pinned cuts, and the set tables up to the device
+    hipStream_t s = ctx->stream;
+    HIPCHK(ctx, hipHostMalloc(&pin.p, (size_t)ns * 8, hipHostMallocDefault));
+    hcuts[0] = (uint32_t *)pin.p, hcuts[1] = hcuts[0] + ns;
+    HIPCHK(ctx, hipMemcpyAsync((void *)tab.off, off, ((size_t)ns + 1) * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync((void *)tab.n_out, res->n_out, (size_t)ns * 8,
+                               hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));  // (the tables are pageable host memory)
+    return RK_OK;
+  }
+  Res len_pass(Save &S, uint64_t k0, uint32_t cnt, uint32_t nb) {
+    const Res r = S.slice(k0);
+    k_outb_len<<<nb, OB, 0, S.ctx->stream>>>(S.cols, tab, r, k0, cnt, crow, S.len8, S.hst,
+                                             S.blk_tot, S.ctr);
+    return Res{crow, r.gid, r.rep};
+  }
+  // the sets whose first slot lies in the chunk, and their cuts on the way down;
+  // the last chunk also takes the empty sets at the very end
+  int after_scan(Save &S, int par, uint64_t k0, uint32_t cnt, Chunk *out) {
+    hipStream_t s = S.ctx->stream;
+    const uint64_t *b = off, *e = off + ns;
+    out->ks = (uint32_t)(std::lower_bound(b, e, k0) - b);
+    out->m = (k0 + cnt >= total ? ns : (uint32_t)(std::lower_bound(b, e, k0 + cnt) - b)) - out->ks;
+    if (!out->m) return RK_OK;
+    k_outb_cuts<<<(out->m + OB - 1) / OB, OB, 0, s>>>(tab.off, out->ks, out->m, k0, cnt, S.len8,
+                                                      S.blk_off, cuts[par]);
+    HIPCHK(S.ctx, hipMemcpyAsync(hcuts[par], cuts[par], (size_t)out->m * 4,
+                                 hipMemcpyDeviceToHost, s));
+    return RK_OK;
+  }
+  int begin_chunk(rk_ctx *ctx, uint64_t k0, const Chunk &c, int par, hipEvent_t put) {
     // the chunk's cuts are down once its put pass is (all but the last chunk's
     // already is: the next chunk's length pass ran behind it)
-    HIPCHK(ctx, hipEventSynchronize(S.ev.e[3 + 2 * par]));
-    if (!files.begin_chunk(off, res->n_out, c * R, cur.cnt, cur.ks, cur.m, S.hcuts[par],
-                           cur.bytes)) {
-      ctx->err = "csv cuts: the sets' text offsets do not lie in the chunk in order";
-      return fail(RK_E_INTERNAL);
-    }
-    rc = rk::io_d2h_sink(ctx, ctx->txt[par], (size_t)cur.bytes, S.ev.e[3 + 2 * par],
-                         [&](const char *p, size_t len, size_t o) { return files.sink(p, len, o); });
-    files.end_chunk();
-    st.d2h_write_ms += rk::wall_ms() - t;
-    if (rc == 1) rc = RK_OK;  // (io_bad says so)
-    if (rc) return fail(rc);
-    float ms = 0;
-    HIPCHK(ctx, hipEventElapsedTime(&ms, S.ev.e[2 + 2 * par], S.ev.e[3 + 2 * par]));
-    st.device_ms += ms;
-    S.patch[par].release();
-    st.bytes += cur.bytes;
-    ++st.chunks;
-    cur = next;
-    if (files.bad != ~0u || files.io_bad) return fail(RK_OK);
+    HIPCHK(ctx, hipEventSynchronize(put));
+    if (files.begin_chunk(off, res->n_out, k0, c.cnt, c.ks, c.m, hcuts[par], c.bytes))
+      return RK_OK;
+    ctx->err = "csv cuts: the sets' text offsets do not lie in the chunk in order";
+    return RK_E_INTERNAL;
   }
-  st.rows = rows;
-  if (files.open_fd >= 0) files.close_file(files.open_fd), files.open_fd = -1;
-  HIPCHK(ctx, hipMemcpyAsync(ctx->host, S.perr, 4, hipMemcpyDeviceToHost, s));
-  HIPCHK(ctx, hipStreamSynchronize(s));
-  if (*ctx->host) {
-    ctx->err = "csv put pass: a block's text does not fit its place";
-    return finish(RK_E_INTERNAL);
+  bool sink(const char *p, size_t len, size_t o) { return files.sink(p, len, o); }
+  void end_chunk(const Chunk &, int, rk_egress_stats *) { files.end_chunk(); }  // (io_bad says so)
+  bool stop() const { return files.bad != ~0u || files.io_bad; }
+  void done(rk_egress_stats *st) {
+    st->rows = rows;
+    if (files.open_fd >= 0) files.close_file(files.open_fd), files.open_fd = -1;
   }
-  return finish(RK_OK);
+  int finish(rk_ctx *ctx, int rc) { return rc ? rc : stop() ? set_io_error(ctx, files) : RK_OK; }
+};
+
+int write_set_device(rk_ctx *ctx, const rk_dbset *dbs, const char *const *paths,
+                     const rk_batch_result *res, uint32_t flags) {
+  SetRoute rt(dbs, paths, res);
+  return write_chunks(ctx, dbs->db, rt, Res{res->out_order, res->gid, res->repval}, rt.total,
+                      flags);
 }
 
 // rk_classify_device_batch on the set's resident columns into DEVICE result
@@ -902,13 +919,10 @@ int dbset_classify_resident(rk_ctx *ctx, const rk_dbset *dbs, double len_ratio, 
   const uint32_t ns = (uint32_t)dbs->header.size();
   const size_t n = dv.n;
   if (n >= 0xFFFFFFFFull) return RK_E_TOO_MANY;
-  rk::Carve pc{nullptr};
-  pc.take<uint32_t>(n), pc.take<uint32_t>(n), pc.take<uint8_t>(n);
-  int rc = rk::grow(ctx, &ctx->io, &ctx->io_cap, pc.off, "result staging");
+  Res r;
+  int rc = carve_result(ctx, &ctx->io, &ctx->io_cap, n, "result staging", &r);
   if (rc) return rc;
-  rk::Carve c{(char *)ctx->io};
-  dres->out_order = c.take<uint32_t>(n), dres->gid = c.take<uint32_t>(n);
-  dres->repval = c.take<uint8_t>(n);
+  dres->out_order = r.order, dres->gid = r.gid, dres->repval = r.rep;
   if (n) {
     HIPCHK(ctx, hipMemsetAsync(dres->out_order, 0, n * 4, ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(dres->gid, 0, n * 4, ctx->stream));
@@ -940,15 +954,10 @@ int check_set_args(rk_ctx *ctx, const rk_dbset *dbs, bool rows, const char *what
 int selected(rk_ctx *ctx, uint32_t ns, const uint64_t *off, const uint64_t *n_out, Res in,
              uint32_t keep, Res *out, uint64_t *kept) {
   const size_t n = ns ? off[ns] : 0;
-  rk::Carve pc{nullptr};
-  pc.take<uint32_t>(n), pc.take<uint32_t>(n), pc.take<uint8_t>(n);
-  int rc = rk::grow(ctx, &ctx->sel, &ctx->sel_cap, pc.off, "selected result");
+  const int rc = carve_result(ctx, &ctx->sel, &ctx->sel_cap, n, "selected result", out);
   if (rc) return rc;
-  rk::Carve c{(char *)ctx->sel};
-  uint32_t *so = c.take<uint32_t>(n), *sg = c.take<uint32_t>(n);
-  uint8_t *sr = c.take<uint8_t>(n);
-  *out = Res{so, sg, sr};
-  return rk::select_device(ctx, ns, off, n_out, in.order, in.gid, in.rep, keep, so, sg, sr, kept);
+  return rk::select_device(ctx, ns, off, n_out, in.order, in.gid, in.rep, keep, out->order,
+                           out->gid, out->rep, kept);
 }
 
 template <class F>
@@ -1037,8 +1046,7 @@ extern "C" int rk_classify_dbset_to_csv_keep(rk_ctx *ctx, const rk_dbset *dbs, d
       if ((rc2 = selected(ctx, ns, dbs->set_off.data(), no.data(),
                           Res{dres.out_order, dres.gid, dres.repval}, keep, &sel, nk.data())))
         return rc2;
-      dres = rk_batch_result{const_cast<uint32_t *>(sel.order), const_cast<uint32_t *>(sel.gid),
-                             const_cast<uint8_t *>(sel.rep), nk.data(), ng.data()};
+      dres = rk_batch_result{sel.order, sel.gid, sel.rep, nk.data(), ng.data()};
     } else {
       nk = no;
     }
@@ -1063,17 +1071,8 @@ extern "C" int rk_db_write_csv_device(rk_ctx *ctx, const rk_db *db, const char *
   ctx->err.clear();
   int rc = check_args(ctx, db, "rk_db_write_csv_device");
   if (rc) return rc;
-  try {
-    return write_device(ctx, db, path, res, flags);
-  } catch (const std::bad_alloc &) {
-    (void)hipStreamSynchronize(ctx->stream);
-    ctx->err = "rk_db_write_csv_device: out of host memory";
-    return RK_E_NOMEM;
-  } catch (...) {
-    (void)hipStreamSynchronize(ctx->stream);
-    ctx->err = "unexpected C++ exception";
-    return RK_E_INTERNAL;
-  }
+  return guarded(ctx, "rk_db_write_csv_device",
+                 [&] { return write_device(ctx, db, path, res, flags); });
 }
 
 extern "C" int rk_classify_db_pairs_to_csv_keep(rk_ctx *ctx, const rk_db *db,
@@ -1090,7 +1089,7 @@ extern "C" int rk_classify_db_pairs_to_csv_keep(rk_ctx *ctx, const rk_db *db,
   int rc = check_args(ctx, db, "rk_classify_db_pairs_to_csv");
   if (rc) return rc;
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  try {
+  return guarded(ctx, "rk_classify_db_pairs_to_csv", [&]() -> int {
     std::vector<rk_result> dres;
     if ((rc = rk::db_classify_resident(ctx, db, len_ratio, pos_ratio, npairs, dres))) return rc;
     for (uint32_t q = 0; q < npairs; ++q) {
@@ -1106,22 +1105,13 @@ extern "C" int rk_classify_db_pairs_to_csv_keep(rk_ctx *ctx, const rk_db *db,
         if ((rc = selected(ctx, 1, off, &r.n_out, Res{r.out_order, r.gid, r.repval}, keep, &sel,
                            &kept)))
           return rc;
-        r = rk_result{const_cast<uint32_t *>(sel.order), const_cast<uint32_t *>(sel.gid),
-                      const_cast<uint8_t *>(sel.rep), kept, r.n_groups};
+        r = rk_result{sel.order, sel.gid, sel.rep, kept, r.n_groups};
       }
       if (n_kept) n_kept[q] = r.n_out;
       if ((rc = write_device(ctx, db, paths[q], &r, RK_RES_DEVICE))) return rc;
     }
     return RK_OK;
-  } catch (const std::bad_alloc &) {
-    (void)hipStreamSynchronize(ctx->stream);
-    ctx->err = "rk_classify_db_pairs_to_csv: out of host memory";
-    return RK_E_NOMEM;
-  } catch (...) {
-    (void)hipStreamSynchronize(ctx->stream);
-    ctx->err = "unexpected C++ exception";
-    return RK_E_INTERNAL;
-  }
+  });
 }
 
 extern "C" int rk_classify_db_pairs_to_csv(rk_ctx *ctx, const rk_db *db, const double *len_ratio,

@@ -493,6 +493,82 @@ def test_context_reuse(corpus, gpu_ctx, tmp_path):
         assert read(a[k]) == read(b[k]) == read(os.path.join(EDGE, n + ".out.csv")), n
 
 
+# ---- 9: one chunk driver, two routes -------------------------------------------------------
+
+ROUTE_ROWS, ROUTE_CHUNK = 300, 129
+
+
+@pytest.fixture(scope="module")
+def two_routes(gpu_ctx, tmp_path_factory):
+    """The same 300 rows (the single route's boundary_rows: shortest rows, longest
+    device rows, a host row in every fourth place) as an rk_db and as a one-set
+    rk_dbset, one synthetic result over all of them, and the host writer's file."""
+    import test_csv_egress_device as single
+    d = tmp_path_factory.mktemp("routes")
+    p = single.write_input(d / "b.csv", single.boundary_rows(ROUTE_ROWS))
+    db = rk.FragmentsDatabase(p, ctx=gpu_ctx, keep_rows=True)
+    dbs = rk.FragmentsDatabaseSet([p], gpu_ctx, keep_rows=True)
+    assert db.frags.n == ROUTE_ROWS and list(dbs.set_off) == [0, ROUTE_ROWS]
+    k = np.arange(ROUTE_ROWS, dtype=np.uint32)
+    res = rk.ClassifyResult((k * 7919).astype(np.uint32), (k % 3).astype(np.uint8), k, ROUTE_ROWS)
+    db.save_all_frag_pairs(str(d / "host.csv"), res)
+    want = read(d / "host.csv")
+    assert len(want.split(b"\n")) == 16 + ROUTE_ROWS + 1
+    yield db, dbs, res, want
+    dbs.close()
+    db.close()
+
+
+def with_order(res, k, value):
+    bad = rk.ClassifyResult(res.gid.copy(), res.repval.copy(), res.out_order.copy(), res.n_groups)
+    bad.out_order[k] = value
+    return bad
+
+
+def test_both_routes_same_bytes(two_routes, gpu_ctx, tmp_path, monkeypatch):
+    """Three chunks of 129 rows: a 128-row block seam inside the first, host rows
+    (every fourth) on both sides of the chunk edges."""
+    db, dbs, res, want = two_routes
+    monkeypatch.setenv("RK_CSV_OUT_ROWS", str(ROUTE_CHUNK))
+    one, batch = tmp_path / "one.csv", tmp_path / "batch.csv"
+    db.save_all_frag_pairs_device(gpu_ctx, str(one), res)
+    st1 = gpu_ctx.egress_stats()
+    dbs.save_all_device(gpu_ctx, [batch], [res])
+    stb = gpu_ctx.egress_stats()
+    assert read(one) == want, "the single route's file differs from the host writer's"
+    assert read(batch) == want, "the batch route's file differs from the host writer's"
+    for key in ("rows", "bytes", "host_rows"):
+        assert st1[key] == stb[key], key
+    assert st1["rows"] == ROUTE_ROWS and st1["host_rows"] == ROUTE_ROWS // 4
+    assert st1["bytes"] == len(want) - len(header(ROUTE_ROWS, 1_000_000_000))
+    n_out, slots = int(res.out_order.shape[0]), int(dbs.set_off[-1])
+    assert st1["chunks"] == -(-n_out // ROUTE_CHUNK) == 3
+    assert stb["chunks"] == -(-slots // ROUTE_CHUNK) == 3
+
+
+def test_error_on_one_route_leaves_the_other_clean(two_routes, gpu_ctx, tmp_path, monkeypatch):
+    """An out_order entry past the rows fails the length pass of the second chunk
+    (RK_E_ARG, by flag) while the first chunk's patch buffer is live; the next
+    write on the same context, through the other route, is whole."""
+    db, dbs, res, want = two_routes
+    monkeypatch.setenv("RK_CSV_OUT_ROWS", str(ROUTE_CHUNK))
+    bad = with_order(res, 200, ROUTE_ROWS)  # (row 200 lies in the second chunk)
+    one, batch = tmp_path / "one.csv", tmp_path / "batch.csv"
+    with pytest.raises(rk.RkError) as e:
+        dbs.save_all_device(gpu_ctx, [batch], [bad])
+    assert e.value.code == -1
+    db.save_all_frag_pairs_device(gpu_ctx, str(one), res)
+    assert read(one) == want
+    assert gpu_ctx.egress_stats()["chunks"] == 3
+    os.remove(one)
+    with pytest.raises(rk.RkError) as e:
+        db.save_all_frag_pairs_device(gpu_ctx, str(one), bad)
+    assert e.value.code == -1
+    dbs.save_all_device(gpu_ctx, [batch], [res])
+    assert read(batch) == want
+    assert gpu_ctx.egress_stats()["chunks"] == 3
+
+
 # ---- 10: CLI ---------------------------------------------------------------------------
 
 CLI_NAMES = ["e01_last_bucket", "e13_no_fragments", "e16_no_final_newline"]
